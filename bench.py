@@ -24,6 +24,11 @@ Prints ONE JSON line on rank 0 with the contract fields plus
                   process AFTER the headline's timed region and never mixed into `value`: `fp8_ffn` (configs[4]'s weight path
                   on the 2B stand-in), `pairs8` (configs[2]'s per-GPU shard: the weak-scaling baseline at N = 1),
                   `c4_112_tiles` (configs[3]).  A failing leg reports its error and leaves the headline alone.
+
+--dump-outputs DIR writes what the LAST timed step computed as DIR/<name>.npy (float32): `packed34`, the [pairs, 2, 34] block a
+step returns (score, 5 aspect scores, 28 rewards per video; the whole batch at N > 1), and every field of rank 0's last forward
+(`score`, `hidden_state`, ...).  Weights and inputs come from fixed seeds, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -331,6 +336,27 @@ def secondary_legs(model, cfg, dev, px, ids, mask):
     return sec
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """``arrays`` {name: tensor} -> ``out_dir``/<name>.npy in float32; returns {name: shape written}.  Past ``max_bytes`` in all,
+    every array keeps the same share of its rows (leading dimension), chosen with a fixed seed: arrays with as many rows keep the
+    same rows, and runs with the same arguments keep the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        if total > max_bytes:   # (1 MiB left over for the .npy headers and the one-row minimum)
+            keep = max(1, a.shape[0] * (max_bytes - (1 << 20)) // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def model_fp8_linears(fmt):
     from mj_video_amd.modeling import FFN_LINEARS, FP8_PRESETS
     return FP8_PRESETS.get(fmt, FFN_LINEARS)
@@ -394,7 +420,11 @@ def main():
                     help="BASELINE configs[4]'s weight path on the 2B stand-in: the five FFN Linears of both towers on MXFP8 (e4m3, "
                          "block-32 e8m0 scales) operands, fp32 accumulate (model.set_ffn_format('mxfp8')).  Its own line, its own "
                          "dtype and tolerance (DESIGN §7.4) - never the default, never the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy in float32 (module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pairs is None:
         args.pairs = 4 if args.gpus == 1 else 8
 
@@ -460,13 +490,14 @@ def main():
     ids, mask = ids.to(dev), mask.to(dev)
     seq_len = int(ids.shape[1])
     global_pairs = list(range(world * args.pairs))   # pair ids of the whole batch; rank r owns a contiguous block of them
+    last_forward = [None]   # the CustomOutput of the latest forward (--dump-outputs)
 
     def score_local(local_pairs):
         # this rank's shard (its own synthetic inputs, resident in HBM).  Fresh id / mask tensors every step, as every real
         # batch brings: the forward pays its device->host copy of the ids (the model caches the host copy only for the
         # SAME unmodified tensor objects)
         assert len(local_pairs) == args.pairs
-        model.forward(px, ids.clone(), mask.clone())
+        last_forward[0] = model.forward(px, ids.clone(), mask.clone())
         return model.last_packed34.view(args.pairs, 2, 34)
 
     def step():
@@ -506,6 +537,10 @@ def main():
     if prof:
         ops.prof_enable(False)
         ops.prof_filter(None)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        fwd = last_forward[0]
+        dumped = dump_outputs(args.dump_outputs, {"packed34": out, **{k: fwd[k] for k in fwd.keys()}})
     if not torch.isfinite(out).all():
         raise SystemExit("non-finite scores")
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -681,6 +716,8 @@ def main():
                                                       "sample": f"1 video (8 tiles @224^2, N={n1}), 1 warm-up + 2 timed, {dt1:.1f}s each"}
             except Exception as e:  # the baseline is informational; never lose the GPU number over it
                 line["cpu_baseline"] = {"value": None, "error": repr(e)}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()

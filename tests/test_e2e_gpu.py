@@ -1344,3 +1344,29 @@ def test_bench_launcher_path_runs_on_one_gpu(cuda):
     assert line["process_group"] == "nccl" and line["ranks_seen"] == 1 and line["n_gpus"] == 1
     assert line["value"] > 0 and line["config"]["global_pairs_per_step"] == 2
     assert line["library"] == {"path": os.path.join("mj-video_amd", "libmjv_hip.so"), "bench_build": False}
+
+
+def test_bench_dump_outputs_on_one_gpu(cuda, tmp_path):
+    """bench.py --dump-outputs: the line states the timed step count it was given, and DIR holds the last timed step's
+    [pairs, 2, 34] block and the forward's fields as float32, consistent with each other (score | aspect scores | rewards).
+    Started as a CHILD process, like the launcher test."""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("MJV_LIBRARY", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "2",
+                        "--no-cpu-baseline", "--no-latency", "--no-secondary", "--dump-outputs", str(tmp_path)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(arrays) == {"packed34"} | set(FIELDS) and line["dump_outputs"]["arrays"] == {k: list(a.shape) for k, a in arrays.items()}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    packed = arrays["packed34"]
+    assert packed.shape == (2, 2, 34) and arrays["hidden_state"].shape[0] == 4
+    assert np.array_equal(packed[..., 0].ravel(), arrays["score"]) and np.array_equal(packed[..., 1:6].reshape(4, 5), arrays["aspect_scores"])
+    rew = arrays["rewards"]
+    assert np.all(np.abs(packed[..., 6:].reshape(4, 28) - rew) <= 2.0 ** -8 * np.abs(rew) + 1e-6)

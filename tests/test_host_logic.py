@@ -527,12 +527,11 @@ def test_label_schema_mappings():
     assert harness.overall_target(1) == ([1], [1]) and harness.overall_target(2) == ([-1], [1]) and harness.overall_target(0) == ([0], [0])
     assert harness.preference_targets({"x": "Video 1 better", "y": "Video 2 better", "z": "tie"}) == ([0, 1, 1], [1, 1, 0])
     assert harness.preference_targets("Video 2 better") == ([1], [1])
-    # the label file shipped with the reference parses with these rules
+    # the label file shipped with the reference parses with these rules (its first record, stored in tests/golden/label_record.json)
     import json
-    path = "/root/reference/datas/test.json"
-    if os.path.isfile(path):
-        rec = json.load(open(path))[0]
-        s, r, names = harness.criteria_targets(rec["video_0_label"])
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "label_record.json")))
+    for key in ("video_0_label", "video_1_label"):
+        s, r, names = harness.criteria_targets(rec[key])
         assert len(s) == len(r) == len(names) == 28 and set(s) <= {-1, 0, 1}
 
 
@@ -694,3 +693,27 @@ def test_committed_gelu_table_equals_torch_for_every_bf16_input():
     got = np.where(mag < LO, half, np.where(mag >= HI, beyond, tab[np.clip(mag - LO, 0, R - 1) + sign * NEG]))
     check = mag >= 0x0100      # every input whose half is a normal number (as tools/gen_gelu_table.py) - infinities and NaNs included
     assert np.array_equal(got[check], want[check]), int((got[check] != want[check]).sum())
+
+
+# ------------------------------------------------------------------------------------------- bench.py --dump-outputs
+def test_bench_dump_outputs_float32_and_capped(tmp_path):
+    """bench.dump_outputs: every array as a float32 .npy, values unchanged; past the byte cap the same seeded rows of every
+    array with as many rows, the same in every run, and the files stay under the cap"""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = {"packed34": torch.randn(4, 2, 34, generator=g), "hidden_state": torch.randn(8, 2048, generator=g).to(torch.bfloat16)}
+    assert bench.dump_outputs(str(tmp_path / "small"), small) == {"packed34": [4, 2, 34], "hidden_state": [8, 2048]}
+    for k, v in small.items():
+        a = np.load(tmp_path / "small" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    big = {"a": torch.randn(4096, 1024, generator=g), "b": torch.randn(4096, 256, generator=g).to(torch.bfloat16)}   # 20 MiB in fp32
+    cap = 4 << 20
+    for run in ("r1", "r2"):
+        shapes = bench.dump_outputs(str(tmp_path / run), big, max_bytes=cap)
+        assert shapes["a"][1:] == [1024] and shapes["b"][1:] == [256] and 1 <= shapes["a"][0] == shapes["b"][0] < 4096
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= cap
+    a, b = (np.load(tmp_path / "r1" / f"{k}.npy") for k in "ab")
+    rows = {float(x): i for i, x in enumerate(big["a"][:, 0].numpy())}
+    idx = [rows[float(x)] for x in a[:, 0]]
+    assert idx == sorted(set(idx)) and np.array_equal(a, big["a"].numpy()[idx]) and np.array_equal(b, big["b"].float().numpy()[idx])
+    assert all(np.array_equal(np.load(tmp_path / "r1" / f"{k}.npy"), np.load(tmp_path / "r2" / f"{k}.npy")) for k in "ab")
