@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: video-pairs scored/sec, MJ-VIDEO-2B, 8 frames @448^2 (max_num=1), bf16.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Called WITHOUT a launcher and with --gpus N > 1 it starts the N ranks itself (a child `python -m torch.distributed.run`
@@ -16,14 +16,19 @@ collective is one RCCL all-gather of the [pairs, 2, 34] fp32 score block (SURVEY
 Prints ONE JSON line on rank 0 with the contract fields plus
   "roofline":     dominant kernel's algorithmic TFLOP/s (HIP events on the launch stream, recorded inside the
                   timed region by the library's opt-in profiler) against the 2.5 PFLOP/s dense bf16 MFMA peak,
+  "kernels":      the per-kernel table of the last warm-up step (events around every launch; --no-prof drops both).
+
+A plain run does only what that line needs: set up, warm up, time the steps, dump (--dump-outputs), print.  --full adds
+what takes runs of its own, after the headline's timed region and never mixed into `value` (--no-cpu-baseline,
+--no-latency and --no-secondary drop one part of it each):
   "cpu_baseline": the oracle (CPU restatement of the reference forward, bf16, LM head included as the
                   reference executes it) timed on this host: 1 warm-up + 2 timed forwards of ONE video, for the C2
                   (headline) and the C1 (224^2) shapes, CPU model / physical cores / threads stated (N=1 only),
   "latency":      one video per forward (the reference's real call pattern, eval_genai_mjvideo.py:140-141), ms,
-  "secondary":    (N=1 default run only) the BASELINE.json configs this command line is not quoted on, measured in the same
-                  process AFTER the headline's timed region and never mixed into `value`: `fp8_ffn` (configs[4]'s weight path
-                  on the 2B stand-in), `pairs8` (configs[2]'s per-GPU shard: the weak-scaling baseline at N = 1),
-                  `c4_112_tiles` (configs[3]).  A failing leg reports its error and leaves the headline alone.
+  "secondary":    (N=1 default configuration only) the BASELINE.json configs this command line is not quoted on, measured in the
+                  same process: `fp8_ffn` / `fp8_rank999` (configs[4]'s weight path on the 2B stand-in), `pairs8` (configs[2]'s
+                  per-GPU shard: the weak-scaling baseline at N = 1), `c4_112_tiles` (configs[3]), `c5_4b` (configs[4]'s backbone),
+                  `prefix_cache_off` (whose value fills `value_all_work`).  A failing leg reports its error and leaves the headline alone.
 
 --dump-outputs DIR writes what the LAST timed step computed as DIR/<name>.npy (float32): `packed34`, the [pairs, 2, 34] block a
 step returns (score, 5 aspect scores, 28 rewards per video; the whole batch at N > 1), and every field of rank 0's last forward
@@ -400,17 +405,21 @@ def main():
     ap.add_argument("--gemm-code", type=int, action="append", default=[],
                     help="A/B switches of the GEMM library (mjv_gemm_set_tile codes, e.g. 4000 = no split-K, 6000 = no skinny "
                          "kernel); not for reported numbers")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: `cpu_baseline`, `latency` and `secondary` "
+                         "(module docstring); a plain run prints the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-latency", action="store_true",
-                    help="skip the single-video latency section (profiling runs: keeps small-batch launches out of the "
+                    help="with --full: skip the single-video latency section (profiling runs: keeps small-batch launches out of the "
                          "per-kernel statistics)")
     ap.add_argument("--no-prof", action="store_true", help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--no-prefix-cache", action="store_true",
                     help="recompute the constant prompt prefix's rows in every forward and every query of the last decoder layer, as "
                          "the reference does (model.prefix_cache = model.trim_last_layer = False); the default line states both "
-                         "switches in `config` and carries this setting as `secondary.prefix_cache_off`")
+                         "switches in `config`, and the --full line carries this setting as `secondary.prefix_cache_off`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` legs (fp8 FFN path, the 8-pair shard, the 112-tile config) of the default N = 1 run")
+                    help="with --full: skip the `secondary` legs (fp8 FFN path, the 8-pair shard, the 112-tile config) of the default "
+                         "N = 1 run")
     ap.add_argument("--backbone", choices=["2b", "4b"], default="2b",
                     help="4b: BASELINE configs[4]'s backbone (InternVL2-4B = InternViT + Phi-3-mini) with the 28-criteria MoE heads instead of "
                          "MJ-VIDEO-2B - its own line (metric, config.baseline_config, its own algorithmic flops), never the headline; with "
@@ -615,7 +624,7 @@ def main():
             line["frac_of_mfma_roofline_note"] = (
                 f"value x executed TFLOP per pair / 2.5 PFLOP/s: {algo_pair:.2f} algorithmic (SURVEY.md §8(d)) minus {left_out:.3f} "
                 "this run leaves out of the language tower (cached prompt-prefix rows in every layer; last decoder layer: q projection + "
-                "attention beyond the rows the heads read, wo / FFN on every other row).  `value_all_work` = the same batch with "
+                "attention beyond the rows the heads read, wo / FFN on every other row).  `value_all_work` (--full) = the same batch with "
                 "prefix_cache / trim_last_layer off (every row in every forward), `frac_all_work` its fraction on ITS executed flops")
             line["pairs_per_s_roofline"] = round(MFMA_BF16_PEAK_TFLOPS * world / algo_pair, 2)
             line["value_all_work"] = None
@@ -667,7 +676,7 @@ def main():
             line["roofline"] = roofline(res, args.steps, share_from=res_all)
             line["roofline"]["note"] = "events around this kernel's launches on the launch stream inside the timed region"
             line["kernels"] = table(res_all, 1)
-        if world == 1 and not args.no_latency and not args.fp8 and not four_b:
+        if args.full and world == 1 and not args.no_latency and not args.fp8 and not four_b:
             # the reference's real call pattern: ONE video per forward (eval_genai_mjvideo.py:140-141), fresh ids each time
             px1, ids1, mask1 = px[:F].contiguous(), ids[:1].contiguous(), mask[:1].contiguous()
             for _ in range(2):
@@ -686,8 +695,9 @@ def main():
             line["latency"] = {"one_video_per_forward_ms": round(lat_ms, 3), "host_enqueue_ms": round(host_ms, 3),
                                "pairs_per_s_at_batch_1_video": round(0.5e3 / lat_ms, 3),
                                "note": "back-to-back single-video forwards, not part of `value`"}
-        if (world == 1 and not use_dist and not args.no_secondary and not args.fp8 and not four_b and (S, F, args.pairs) == (448, 8, 4)
-                and not os.environ.get("MJV_BENCH_NORM_FUSION") and not os.environ.get("MJV_BENCH_VIT_CHUNK") and not args.gemm_code):
+        if (args.full and world == 1 and not use_dist and not args.no_secondary and not args.fp8 and not four_b
+                and (S, F, args.pairs) == (448, 8, 4) and not os.environ.get("MJV_BENCH_NORM_FUSION")
+                and not os.environ.get("MJV_BENCH_VIT_CHUNK") and not args.gemm_code):
             line["secondary"] = secondary_legs(model, cfg, dev, px, ids, mask)
             off = line["secondary"].get("prefix_cache_off")
             if off and off.get("value"):
@@ -695,10 +705,10 @@ def main():
                 line["value_all_work"] = off["value"]
                 line["frac_all_work"] = round(off["value"] * (ALGO_TFLOP_PER_PAIR - lo) / MFMA_BF16_PEAK_TFLOPS, 4)
                 off["frac_of_mfma_roofline"] = line["frac_all_work"]
-        if world == 1 and (args.fp8 or four_b):
-            line["cpu_baseline"] = {"value": None, "note": "timed on the headline line only (default `python bench.py`: the oracle's bf16 forward of "
-                                                            "MJ-VIDEO-2B on the host cores); this line is a secondary configuration"}
-        if world == 1 and not args.no_cpu_baseline and not args.fp8 and not four_b:
+        if args.full and world == 1 and (args.fp8 or four_b):
+            line["cpu_baseline"] = {"value": None, "note": "timed on the headline line only (`python bench.py --full`: the oracle's bf16 forward "
+                                                            "of MJ-VIDEO-2B on the host cores); this line is a secondary configuration"}
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.fp8 and not four_b:
             # oneDNN bf16 GEMMs stop scaling (and oversubscribe NUMA domains) far below a 256-thread host: cap at 32
             cpu_model, phys, logical = host_cpu_info()
             threads = min(phys, 32)

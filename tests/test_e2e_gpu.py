@@ -1370,3 +1370,28 @@ def test_bench_dump_outputs_on_one_gpu(cuda, tmp_path):
     assert np.array_equal(packed[..., 0].ravel(), arrays["score"]) and np.array_equal(packed[..., 1:6].reshape(4, 5), arrays["aspect_scores"])
     rew = arrays["rewards"]
     assert np.all(np.abs(packed[..., 6:].reshape(4, 28) - rew) <= 2.0 ** -8 * np.abs(rew) + 1e-6)
+
+
+def test_bench_plain_line_is_lean_and_full_adds_the_extras(cuda):
+    """A plain bench.py run prints the headline line and nothing that takes runs of its own: no `cpu_baseline`, `latency` or
+    `secondary`; --full adds them after the timed steps (here `latency`: --no-cpu-baseline keeps the oracle's CPU forwards out,
+    and the `secondary` legs run at the headline's own configuration only).  Both runs time the same steps on the same inputs.
+    Started as CHILD processes, like the launcher test."""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("MJV_LIBRARY", None)
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "2"]
+                           + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "bf16" and "roofline" in line
+    assert not {"cpu_baseline", "latency", "secondary"} & set(plain)
+    assert full["latency"]["one_video_per_forward_ms"] > 0 and not {"cpu_baseline", "secondary"} & set(full)

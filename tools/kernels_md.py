@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Writes KERNELS.md - the one-page state of the kernels - from a bench.py line (the per-kernel table of its profiled step and
-the `secondary` legs) plus the fixed text below.  usage: kernels_md.py profiles/rNN_x_bench_default.json [driver BENCH_rNN.json]"""
+"""Writes KERNELS.md - the one-page state of the kernels - from a `bench.py --full` line (the per-kernel table of its profiled step
+and the `secondary` legs) plus the fixed text below.  usage: kernels_md.py profiles/rNN_x_bench_default.json [driver BENCH_rNN.json]"""
 import json
 import os
 import sys
