@@ -32,6 +32,9 @@
  * lets MJV_EPI_ROPE_QKV run with rope_group 0 (a k | v projection without q heads).
  * ABI 7 adds what the Phi-3-mini language tower of BASELINE configs[4] needs beyond the InternLM2 one: head_dim 96 in
  * mjv_attention_bf16 and mjv_rope_heads_bf16 (rotary embedding in place on a [q | k | v] projection).
+ * ABI 7, additive (MJV_ABI_VERSION stays 7: nothing existing changes): mjv_attention_ctx_bf16 with its plan / workspace queries -
+ * causal attention of few own rows per sequence over long key / value contexts that many sequences share (the caption pass of
+ * model.score_captions).
  */
 #ifndef MJV_H_
 #define MJV_H_
@@ -211,6 +214,60 @@ typedef struct mjv_attn_desc {
 int mjv_attention_bf16(const mjv_attn_desc* d, void* stream);
 /* max_seqlen MUST be >= the longest sequence of cu_seqlens: query rows beyond it are not computed (their O rows are left
  * untouched). */
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7, additive - caption-pass attention: every sequence has a few OWN rows (1 - 200) and a long CONTEXT of keys / values
+ * (2 000 - 28 000) that it shares with other sequences of the launch (a video's system + frame tokens under M captions).
+ * Keys of sequence s = [rows cu_context[c] .. cu_context[c + 1] of ctx_k / ctx_v, c = context_index[s] | its own rows of K / V],
+ * causal: local query i sits at key position context_len + own_rows - queries + i.  head_dim 128, GQA, score_round_mode 1 / 2
+ * with the rounding points of mjv_attention_bf16 (scores as there, P rounded to bf16 before P V, fp32 accumulation); any other
+ * head_dim and non-causal launches: MJV_E_UNSUPPORTED.
+ *   Q / K / V / O : the own rows, addressed as in mjv_attn_desc - cu_seqlens: K / V rows; cu_seqlens_q, optional: the queries are
+ *       the LAST cu_seqlens_q[s + 1] - cu_seqlens_q[s] own rows, packed at those rows of Q / O.
+ *   ctx_k / ctx_v : every context's rows in one packed buffer each, with leading dimensions and head strides of their own;
+ *       a context's length is a positive multiple of 64.
+ *   cu_seqlens / cu_seqlens_q / context_index / cu_context are HOST arrays, read during the call only: every shape is checked
+ *       on the host before anything is launched.  What the kernels read is the PLAN, a device copy of the int32 array
+ *       mjv_attention_ctx_plan() derives from exactly these arrays (n_heads, kv_group and head_dim included): the caller builds
+ *       it once per batch, uploads it, and hands it to every layer's call.  A plan from other index arrays is the caller's error
+ *       (the entry can check its size only).
+ *   How the work is laid out: the context part has no mask, so the queries of all sequences of a context and the kv_group
+ *       q-heads of a kv head are stacked into tiles of 128 rows that stage a 64-key K / V tile once; a context's keys are cut
+ *       into pieces (a function of that context's own query count and length, so a sequence's bits do not depend on sequences
+ *       of other contexts) that run as workgroups of their own and leave fp32 (offset, row sum, O) partials in `workspace`; the
+ *       causal part over the own rows is one more partial; a second launch on the same stream merges a row's partials in a
+ *       fixed order and writes bf16.  No atomics, no flags: equal bits run to run.  The library allocates nothing.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mjv_attn_ctx_desc {
+  const mjv_bf16 *Q, *K, *V;
+  mjv_bf16* O;
+  int64_t ldq, ldk, ldv, ldo;
+  int32_t q_head_stride, k_head_stride, v_head_stride, o_head_stride;
+  const mjv_bf16 *ctx_k, *ctx_v;
+  int64_t ld_ctx_k, ld_ctx_v;
+  int32_t ctx_k_head_stride, ctx_v_head_stride;
+  const int32_t* cu_seqlens;     /* HOST [n_seqs + 1] own K / V row offsets, cu_seqlens[0] = 0 */
+  const int32_t* cu_seqlens_q;   /* HOST [n_seqs + 1] or NULL (queries = all own rows) */
+  const int32_t* context_index;  /* HOST [n_seqs] */
+  const int32_t* cu_context;     /* HOST [n_contexts + 1] row offsets into ctx_k / ctx_v */
+  int32_t n_seqs, n_contexts;
+  int32_t n_heads, kv_group;
+  int32_t head_dim;              /* 128 */
+  int32_t causal;                /* 1 */
+  float scale;
+  int32_t score_round_mode;      /* 1 or 2 */
+  const int32_t* plan;           /* DEVICE copy of mjv_attention_ctx_plan's output for these index arrays */
+  int64_t plan_ints;
+  void* workspace;               /* DEVICE, 16-byte aligned, private to this stream while the call is in flight */
+  int64_t workspace_bytes;       /* >= mjv_attention_ctx_workspace_bytes(d) */
+} mjv_attn_ctx_desc;
+
+/* Reads the index arrays and sizes of `d` only (no device pointer).  plan_host == NULL: returns the number of int32 the plan
+ * takes; otherwise writes it (plan_ints = capacity) and returns the number written.  Negative = MJV_E_*. */
+int64_t mjv_attention_ctx_plan(const mjv_attn_ctx_desc* d, int32_t* plan_host, int64_t plan_ints);
+/* bytes of fp32 partials the launch described by `d` (index arrays and sizes only) needs; negative = MJV_E_* */
+int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d);
+int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream);
 
 /* LayerNorm over the last dim, fp32 statistics, bf16 out (nn.LayerNorm on bf16:
  * modeling_intern_vit.py:291,293; modeling_internvl_chat.py:136).

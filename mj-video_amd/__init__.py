@@ -12,6 +12,7 @@ _LAZY = {
     "InternVLChatRewardModeling": ("modeling", "InternVLChatRewardModeling"),
     "InternVLChatModel": ("modeling", "InternVLChatModel"),
     "CustomOutput": ("modeling", "CustomOutput"),
+    "VideoContext": ("modeling", "VideoContext"),
     "load_video": ("video", "load_video"),
 }
 

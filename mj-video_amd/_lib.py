@@ -55,6 +55,20 @@ class AttnDesc(C.Structure):
                 ("prefix_k", C.c_void_p), ("prefix_v", C.c_void_p)]
 
 
+class AttnCtxDesc(C.Structure):
+    """mjv_attn_ctx_desc (ABI 7, additive): the index arrays are HOST pointers, ``plan`` / ``workspace`` device pointers"""
+    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p),
+                ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("ldo", C.c_int64),
+                ("q_head_stride", C.c_int32), ("k_head_stride", C.c_int32), ("v_head_stride", C.c_int32),
+                ("o_head_stride", C.c_int32), ("ctx_k", C.c_void_p), ("ctx_v", C.c_void_p),
+                ("ld_ctx_k", C.c_int64), ("ld_ctx_v", C.c_int64), ("ctx_k_head_stride", C.c_int32),
+                ("ctx_v_head_stride", C.c_int32), ("cu_seqlens", C.c_void_p), ("cu_seqlens_q", C.c_void_p),
+                ("context_index", C.c_void_p), ("cu_context", C.c_void_p), ("n_seqs", C.c_int32), ("n_contexts", C.c_int32),
+                ("n_heads", C.c_int32), ("kv_group", C.c_int32), ("head_dim", C.c_int32), ("causal", C.c_int32),
+                ("scale", C.c_float), ("score_round_mode", C.c_int32), ("plan", C.c_void_p), ("plan_ints", C.c_int64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class HeadsDesc(C.Structure):
     _fields_ = [("hr", C.c_void_p), ("hg", C.c_void_p), ("ldh", C.c_int64), ("hidden", C.c_int32),
                 ("ga", C.c_void_p), ("gc", C.c_void_p), ("ldg", C.c_int64), ("gate_hidden", C.c_int32),
@@ -76,6 +90,9 @@ SYMBOLS = {
     "mjv_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), _VP]),
     "mjv_gemm_workspace_bytes": (C.c_int64, []),
     "mjv_attention_bf16": (C.c_int, [C.POINTER(AttnDesc), _VP]),
+    "mjv_attention_ctx_plan": (C.c_int64, [C.POINTER(AttnCtxDesc), _VP, _I64]),
+    "mjv_attention_ctx_workspace_bytes": (C.c_int64, [C.POINTER(AttnCtxDesc)]),
+    "mjv_attention_ctx_bf16": (C.c_int, [C.POINTER(AttnCtxDesc), _VP]),
     "mjv_layernorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, _VP]),
     "mjv_rmsnorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _VP]),
     "mjv_mxfp8_scale_bytes": (C.c_int64, [_I64, _I64]),

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include <utility>
 #include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -1295,4 +1296,471 @@ extern "C" int mjv_attention_bf16(const mjv_attn_desc* d, void* stream) {
   if (d->causal) { MjvProfScope ps("attn_d128_causal", s, flops, 0); return launch<128, true>(a, d->n_seqs, max_q, d->kernel, s); }
   MjvProfScope ps("attn_d128", s, flops, 0);
   return launch<128, false>(a, d->n_seqs, d->max_seqlen, d->kernel, s);
+}
+
+// =====================================================================================================================
+// Caption-pass attention (ABI 7, additive): few own rows per sequence over long key / value CONTEXTS that many sequences share
+// (mjv_attention_ctx_bf16; include/mjv.h).  A sequence's keys are [its context | its own rows]; the context part carries no
+// mask, so the launch stacks the queries of every sequence of a context AND the kv_group q-heads of a kv head into tiles of
+// 128 MFMA columns ("stacked rows": row r of a tile = query slot r / G, q-head r % G) and splits the context's keys over
+// workgroups: one workgroup = one PART = (tile, key range) of one kv head, a K / V tile of 64 keys staged once for all 128
+// stacked rows.  The causal part over a sequence's own rows is one more part per 128 / G of its queries.  Every part leaves
+// its online-softmax state (integer offset m in exp2 units, row sum l, fp32 O) in the caller's workspace; a second launch on
+// the same stream merges a row's parts in a fixed order (context pieces by ascending key, then the own part) and writes bf16.
+// No flags, no atomics: equal bits run to run.  Which rows share a tile and where a context is cut depends on that context's
+// own sequences and length alone (ctx_plan_build), so a sequence's bits do not move when other contexts join the launch.
+//
+// The arithmetic of a (query, key) unit is attn2_kernel's general path: S^T = K Q^T with v_mfma_f32_32x32x16_bf16 (a lane owns
+// one stacked row), the optimistic integer-offset softmax (HEADROOM, BIGSUM, row sums of the ROUNDED probabilities), P in bf16
+// as the B operand of O^T = V^T P^T, the same LDS image (unpadded rows, chunk swizzles swz_k / swz_v) read with ds_read_b128 /
+// ds_read_b64_tr_b16.  Because the offsets are integers the merge scales by exact powers of two: fp32 partials and an fp32
+// merge add no rounding point to what one walk over [context | own] computes.
+// K / V tiles are register-staged (global -> VGPR -> swizzled ds_write_b128, the next tile's loads in flight under the math):
+// cdna_hip_programming.md measured LDS-DMA at <= 0 against register staging for an attention forward outside hand-scheduled
+// assembly, and a part walks only a handful of tiles.
+// =====================================================================================================================
+namespace {
+namespace cx {
+using namespace v2;
+
+constexpr int TR = 128;            // stacked rows per tile (4 waves x 32 MFMA columns)
+constexpr int PLAN_MAGIC = 0x43545837;
+constexpr int HDR = 8, PART_INTS = 4, TILE_INTS = 8;
+constexpr int MAX_SPLIT = 64;      // pieces a context is cut into at most
+constexpr int TARGET_WG = 512;     // workgroups the context part of one context aims for (2 per CU of an MI355X)
+
+struct CtxArgs {
+  const u16 *Q, *K, *V;
+  u16* O;
+  long ldq, ldk, ldv, ldo;
+  int qhs, khs, vhs, ohs;
+  const u16 *Kc, *Vc;
+  long ldkc, ldvc;
+  int kchs, vchs;
+  const int* plan;
+  float* ws_ml;     // [slab][TR][2]
+  float* ws_acc;    // [slab][TR][D]
+  int n_kv, G, n_heads;
+  int n_parts, n_tiles, total_q;
+  float scale;
+};
+
+// plan layout (int32): header | parts [n_parts][PART_INTS] | tiles [n_tiles][TILE_INTS] | rowq [n_tiles][TR / G] |
+// rowpos [n_tiles][TR / G] | qinfo [total_q][2]
+//   header : {format tag, n_parts, n_tiles, total_q, G, n_kv, 0, 0} - for whoever reads a plan on the host (the tests do); the
+//            kernels get these counts as arguments and never read the header
+//   part   : {tile, first key, end key, 0}
+//   tile   : {0 context / 1 own, first K / V row, keys (host readers only), first part, parts, stacked rows, 0, 0}
+MJV_DEV const int* plan_parts(const CtxArgs& p) { return p.plan + HDR; }
+MJV_DEV const int* plan_tiles(const CtxArgs& p) { return plan_parts(p) + (long)p.n_parts * PART_INTS; }
+MJV_DEV const int* plan_rowq(const CtxArgs& p) { return plan_tiles(p) + (long)p.n_tiles * TILE_INTS; }
+MJV_DEV const int* plan_rowpos(const CtxArgs& p) { return plan_rowq(p) + (long)p.n_tiles * (TR / p.G); }
+MJV_DEV const int* plan_qinfo(const CtxArgs& p) { return plan_rowpos(p) + (long)p.n_tiles * (TR / p.G); }
+
+template <int D, int RM>
+__global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
+  constexpr int PK = D * 2, KBYTES = KB * PK, F = D / 16, CH = D / 8;
+  constexpr int NL = KB * CH / 256;                    // 16-byte chunks per thread, tile and operand
+  __shared__ __attribute__((aligned(16))) char smem[2 * KBYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int part = blockIdx.x / p.n_kv, kvh = blockIdx.x % p.n_kv;
+  const int* pe = plan_parts(p) + (long)part * PART_INTS;
+  const int tile = pe[0], k0 = pe[1], k1 = pe[2];
+  const int* te = plan_tiles(p) + (long)tile * TILE_INTS;
+  const bool own = te[0] != 0;
+  const int key_row0 = te[1], n_rows = te[5];
+  const int QS = TR / p.G;
+
+  const u16* Kg = own ? p.K + (long)kvh * p.khs + (long)key_row0 * p.ldk : p.Kc + (long)kvh * p.kchs + (long)key_row0 * p.ldkc;
+  const u16* Vg = own ? p.V + (long)kvh * p.vhs + (long)key_row0 * p.ldv : p.Vc + (long)kvh * p.vchs + (long)key_row0 * p.ldvc;
+  const long ldk = own ? p.ldk : p.ldkc, ldv = own ? p.ldv : p.ldvc;
+
+  // this lane's stacked row
+  const int r = wave * 32 + l31;
+  const bool active = wave * 32 < n_rows;              // wave-uniform: the wave holds at least one stacked row
+  const bool valid = r < n_rows;
+  const int rc = valid ? r : 0;                        // (rows past the end compute on row 0's query; never written)
+  const int slot = rc / p.G, g = rc % p.G;
+  const int q_row = plan_rowq(p)[(long)tile * QS + slot];
+  const int pos = own ? plan_rowpos(p)[(long)tile * QS + slot] : 0x7fffffff;   // last key position this row sees
+  const int last_slot = (min(wave * 32 + 31, max(n_rows, 1) - 1)) / p.G;
+  const int wave_maxpos = own ? plan_rowpos(p)[(long)tile * QS + last_slot] : 0x7fffffff;   // wave-uniform (positions ascend)
+
+  constexpr float LOG2E = 1.4426950408889634f;
+  const float c_exp = (RM == RM_FLASH) ? p.scale * LOG2E : LOG2E;
+  const f32x2 c2 = {c_exp, c_exp};
+  const f32x2 scale2 = {p.scale, p.scale};
+
+  bf16x8 qf[F];
+  {
+    const u16* qp = p.Q + (long)q_row * p.ldq + (long)(kvh * p.G + g) * p.qhs + 8 * hi;
+#pragma unroll
+    for (int ks = 0; ks < F; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
+  }
+  f32x16 oacc[D / 32];
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) oacc[i][q] = 0.f;
+  float Mq = -INFINITY, lsum = 0.f;
+
+  // fragment offsets: attn2_kernel's LDS image
+  int koff[F], vboff[D / 32];
+  {
+    const int ksw = swz_k<D>(l31);
+#pragma unroll
+    for (int ks = 0; ks < F; ++ks) koff[ks] = l31 * PK + (((hi + 2 * ks) ^ ksw) << 4);
+    const int li = lane & 15, g16 = (lane >> 4) & 1, trow = li >> 2, tcol = 4 * (li & 3);
+    const int svl = swz_v<D>(trow);
+#pragma unroll
+    for (int gg = 0; gg < D / 32; ++gg)
+      vboff[gg] = (4 * hi + trow) * PK + (((gg * 4 + g16 * 2 + (tcol >> 3)) ^ svl) << 4) + (tcol & 7) * 2;
+  }
+  const char* const Ksb = smem;
+  const char* const Vsb = smem + KBYTES;
+  auto read_k = [&](int h, int ks, bf16x8& f) __attribute__((always_inline)) { f = *(const bf16x8*)(Ksb + h * 32 * PK + koff[ks]); };
+  auto read_v = [&](int h, int f_, bf16x8& f) __attribute__((always_inline)) {
+    const char* vp = Vsb + vboff[f_ >> 1] + (2 * h + (f_ & 1)) * 16 * PK;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp));
+    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp + 8 * PK));
+    const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+    f = __builtin_bit_cast(bf16x8, v8);
+  };
+  auto do_pair = [&](const f32x16& S, int q, float nmb, float& psum, unsigned& pw) __attribute__((always_inline)) {
+    const f32x2 a2 = {S[q], S[q + 1]};
+    f32x2 sr;
+    if constexpr (RM == RM_FLASH) sr = a2;
+    else sr = round_pair(round_pair(a2) * scale2);      // RM_DIV: bf16(bf16(acc) * scale)
+    const f32x2 e2 = sr * c2 + f32x2{nmb, nmb};
+    const f32x2 pv = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};
+    pw = pack_pair(pv);
+    psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, pw), __builtin_bit_cast(bf16x2v, 0x3f803f80u), psum, false);
+  };
+  auto redo = [&](const f32x16& S, float& psum, unsigned (&pw)[8]) __attribute__((always_inline)) {
+    float mx = S[0];
+#pragma unroll
+    for (int q = 1; q < 16; ++q) mx = fmaxf(mx, S[q]);
+    mx = xhalf_max(mx);
+    const float arg = round_score<RM>(mx, p.scale) * c_exp;
+    float mn = fmaxf(Mq, ceilf(arg) + HEADROOM);
+    if (!(mn > -INFINITY)) mn = 0.f;
+    const float alpha = __builtin_amdgcn_exp2f(Mq - mn);
+    lsum *= alpha;
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) oacc[i][q] *= alpha;
+    Mq = mn;
+    psum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; q += 2) do_pair(S, q, -mn, psum, pw[q >> 1]);
+  };
+
+  // staging: chunk i of this thread = slot i * 256 + tid -> (row, 16-byte chunk); rows past k1 (own parts only: a context
+  // piece is whole tiles) re-read the last key and are masked
+  u32x4 kreg[NL], vreg[NL];
+  auto load_tile = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int s = i * 256 + tid, row = s / CH, cl = s % CH;
+      const int gr = min(kt + row, k1 - 1);
+      kreg[i] = *(const u32x4*)(Kg + (long)gr * ldk + cl * 8);
+      vreg[i] = *(const u32x4*)(Vg + (long)gr * ldv + cl * 8);
+    }
+  };
+  auto store_tile = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int s = i * 256 + tid, row = s / CH, cl = s % CH;
+      *(u32x4*)(smem + row * PK + ((cl ^ swz_k<D>(row)) << 4)) = kreg[i];
+      *(u32x4*)(smem + KBYTES + row * PK + ((cl ^ swz_v<D>(row)) << 4)) = vreg[i];
+    }
+  };
+
+  load_tile(k0);
+  for (int kt = k0; kt < k1; kt += KB) {
+    __syncthreads();                 // every wave is done with the previous tile
+    store_tile();
+    __syncthreads();
+    if (kt + KB < k1) load_tile(kt + KB);
+    if (!active) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int kb = kt + 32 * h;
+      if (kb >= k1 || kb > wave_maxpos) continue;      // wave-uniform
+      bf16x8 kf[F], vf[F];
+#pragma unroll
+      for (int ks = 0; ks < F; ++ks) read_k(h, ks, kf[ks]);
+      f32x16 S;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) S[q] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < F; ++ks) S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], S, 0, 0, 0);
+      if (own) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int key = kb + (q & 3) + 8 * (q >> 2) + 4 * hi;
+          if (key >= k1 || key > pos) S[q] = -INFINITY;
+        }
+      }
+      unsigned pw[8];
+      float ps = 0.f;
+      const float nmb = -Mq;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) do_pair(S, q, nmb, ps, pw[q >> 1]);
+      if (__any(!(ps < BIGSUM))) redo(S, ps, pw);
+      lsum += ps;
+#pragma unroll
+      for (int f_ = 0; f_ < F; ++f_) read_v(h, f_, vf[f_]);
+#pragma unroll
+      for (int f_ = 0; f_ < F; ++f_) {
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, u32x4{pw[4 * (f_ & 1)], pw[4 * (f_ & 1) + 1], pw[4 * (f_ & 1) + 2], pw[4 * (f_ & 1) + 3]});
+        oacc[f_ >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[f_], pf, oacc[f_ >> 1], 0, 0, 0);
+      }
+    }
+  }
+
+  // the part's state of this stacked row: register q of oacc[dt] <-> d = 32 dt + (q & 3) + 8 (q >> 2) + 4 hi
+  const float l = xhalf_sum(lsum);
+  if (!valid) return;
+  const long rec = ((long)part * p.n_kv + kvh) * TR + r;
+  if (hi == 0) *(f32x2*)(p.ws_ml + rec * 2) = f32x2{Mq, l};
+  float* ap = p.ws_acc + rec * D;
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4)
+      *(f32x4*)(ap + dt * 32 + 8 * g4 + 4 * hi) = f32x4{oacc[dt][4 * g4], oacc[dt][4 * g4 + 1], oacc[dt][4 * g4 + 2], oacc[dt][4 * g4 + 3]};
+}
+
+// merge of a (query row, q-head)'s parts: 32 lanes per pair, D / 32 consecutive elements per lane
+template <int D>
+__global__ __launch_bounds__(256) void attn_ctx_combine_kernel(CtxArgs p) {
+  constexpr int E = D / 32;
+  const int pair = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
+  if (pair >= p.total_q * p.n_heads) return;
+  const int q_row = pair / p.n_heads, head = pair % p.n_heads;
+  const int kvh = head / p.G, g = head % p.G;
+  const int QS = TR / p.G;
+  const int* qi = plan_qinfo(p) + (long)q_row * 2;
+  // the row's parts in merge order: the context tile's pieces by ascending key, then the own part
+  auto for_each_part = [&](auto&& fn) __attribute__((always_inline)) {
+#pragma unroll 1
+    for (int w = 0; w < 2; ++w) {
+      const int sc = qi[w];
+      const int* te = plan_tiles(p) + (long)(sc / QS) * TILE_INTS;
+      const int part0 = te[3], ns = te[4];
+      const int r = (sc % QS) * p.G + g;
+      for (int s = 0; s < ns; ++s) fn(((long)(part0 + s) * p.n_kv + kvh) * TR + r);
+    }
+  };
+  float m = -INFINITY;
+  for_each_part([&](long rec) __attribute__((always_inline)) { m = fmaxf(m, p.ws_ml[rec * 2]); });
+  float lsum = 0.f, acc[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) acc[e] = 0.f;
+  for_each_part([&](long rec) __attribute__((always_inline)) {
+    const f32x2 ml = *(const f32x2*)(p.ws_ml + rec * 2);
+    const float a = __builtin_amdgcn_exp2f(ml[0] - m);     // integer offsets: an exact power of two
+    lsum += ml[1] * a;
+    const f32x4 v = *(const f32x4*)(p.ws_acc + rec * D + l * E);
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[e] += v[e] * a;
+  });
+  const float inv = 1.0f / lsum;
+  u16* op = p.O + (long)q_row * p.ldo + (long)head * p.ohs + l * E;
+  static_assert(E == 4, "one 8-byte store per lane");
+  *(u32x2*)op = u32x2{pack2bf(acc[0] * inv, acc[1] * inv), pack2bf(acc[2] * inv, acc[3] * inv)};
+}
+
+struct PlanInfo {
+  long n_parts = 0, n_tiles = 0, total_q = 0, ints = 0, ws_bytes = 0;
+  double pairs = 0;   // (query, key) pairs per q-head
+};
+
+// Validates the index arrays (HOST) of a descriptor and lays the plan out; `out` == nullptr: sizes only.
+int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
+  MJV_REQUIRE(d && d->cu_seqlens && d->context_index && d->cu_context, "attention_ctx: null index array (cu_seqlens / context_index / cu_context are host arrays)");
+  MJV_REQUIRE(d->n_seqs > 0 && d->n_contexts > 0 && d->n_heads > 0 && d->kv_group > 0, "attention_ctx: bad sizes");
+  MJV_REQUIRE(d->n_heads % d->kv_group == 0, "attention_ctx: n_heads %% kv_group != 0");
+  const int G = d->kv_group, n_kv = d->n_heads / G;
+  MJV_REQUIRE(TR % G == 0, "attention_ctx: kv_group %d must divide %d", G, TR);
+  if (d->head_dim != 128) {
+    mjv_set_error("attention_ctx: head_dim %d is not built (128 only)", d->head_dim);
+    return MJV_E_UNSUPPORTED;
+  }
+  const int QS = TR / G;
+  MJV_REQUIRE(d->cu_seqlens[0] == 0 && (!d->cu_seqlens_q || d->cu_seqlens_q[0] == 0), "attention_ctx: cu_seqlens / cu_seqlens_q start at 0");
+  MJV_REQUIRE(d->cu_context[0] >= 0, "attention_ctx: cu_context[0] < 0");
+  for (int c = 0; c < d->n_contexts; ++c) {
+    const long len = (long)d->cu_context[c + 1] - d->cu_context[c];
+    MJV_REQUIRE(len > 0 && len % KB == 0, "attention_ctx: context %d has %ld keys - a positive multiple of %d is required", c, len, KB);
+  }
+  long total_q = 0;
+  for (int s = 0; s < d->n_seqs; ++s) {
+    const int len = d->cu_seqlens[s + 1] - d->cu_seqlens[s];
+    const int lq = d->cu_seqlens_q ? d->cu_seqlens_q[s + 1] - d->cu_seqlens_q[s] : len;
+    MJV_REQUIRE(len > 0 && lq > 0 && lq <= len, "attention_ctx: sequence %d has %d own rows and %d queries (1 <= queries <= rows)", s, len, lq);
+    MJV_REQUIRE(d->context_index[s] >= 0 && d->context_index[s] < d->n_contexts, "attention_ctx: sequence %d names context %d of %d", s,
+                d->context_index[s], d->n_contexts);
+    total_q += lq;
+  }
+  MJV_REQUIRE(total_q * (long)d->n_heads < (1l << 30), "attention_ctx: too many query rows");
+  // pass 1: counts
+  long n_ctx_tiles = 0, n_own_tiles = 0, n_parts = 0;
+  std::vector<long> ctx_q(d->n_contexts, 0);
+  double pairs = 0;
+  for (int s = 0; s < d->n_seqs; ++s) {
+    const int len = d->cu_seqlens[s + 1] - d->cu_seqlens[s];
+    const int lq = d->cu_seqlens_q ? d->cu_seqlens_q[s + 1] - d->cu_seqlens_q[s] : len;
+    const int c = d->context_index[s];
+    ctx_q[c] += lq;
+    n_own_tiles += (lq + QS - 1) / QS;
+    const double clen = (double)d->cu_context[c + 1] - d->cu_context[c];
+    pairs += lq * clen + (double)lq * (len - lq) + 0.5 * lq * (lq + 1.0);
+  }
+  std::vector<int> ctx_split(d->n_contexts, 0), ctx_chunk(d->n_contexts, 0);
+  for (int c = 0; c < d->n_contexts; ++c) {
+    if (!ctx_q[c]) continue;
+    const long tiles = (ctx_q[c] + QS - 1) / QS;
+    const int kt = (d->cu_context[c + 1] - d->cu_context[c]) / KB;
+    // where a context is cut depends on ITS tiles and length alone; pieces of at least two key tiles
+    long want = (TARGET_WG + tiles * n_kv - 1) / (tiles * n_kv);
+    want = std::max(1l, std::min({want, (long)MAX_SPLIT, (long)std::max(1, kt / 2)}));
+    const int chunk_t = (int)((kt + want - 1) / want);
+    ctx_chunk[c] = chunk_t * KB;
+    ctx_split[c] = (kt + chunk_t - 1) / chunk_t;
+    n_ctx_tiles += tiles;
+    n_parts += tiles * ctx_split[c];
+  }
+  n_parts += n_own_tiles;
+  const long n_tiles = n_ctx_tiles + n_own_tiles;
+  info->n_parts = n_parts; info->n_tiles = n_tiles; info->total_q = total_q; info->pairs = pairs;
+  info->ints = HDR + n_parts * PART_INTS + n_tiles * TILE_INTS + 2 * n_tiles * QS + 2 * total_q;
+  info->ws_bytes = n_parts * n_kv * TR * (long)(d->head_dim + 2) * 4;
+  MJV_REQUIRE(n_parts * n_kv < (1l << 30) && info->ints < (1l << 31), "attention_ctx: launch too large");
+  if (!out) return MJV_OK;
+  // pass 2: fill
+  int32_t* parts = out + HDR;
+  int32_t* tiles = parts + n_parts * PART_INTS;
+  int32_t* rowq = tiles + n_tiles * TILE_INTS;
+  int32_t* rowpos = rowq + n_tiles * QS;
+  int32_t* qinfo = rowpos + n_tiles * QS;
+  out[0] = PLAN_MAGIC; out[1] = (int32_t)n_parts; out[2] = (int32_t)n_tiles; out[3] = (int32_t)total_q; out[4] = G; out[5] = n_kv;
+  out[6] = out[7] = 0;
+  for (long i = 0; i < 2 * n_tiles * QS; ++i) rowq[i] = 0;
+  long t = 0, pt = 0;
+  for (int c = 0; c < d->n_contexts; ++c) {
+    if (!ctx_q[c]) continue;
+    const int clen = d->cu_context[c + 1] - d->cu_context[c];
+    long j = 0;      // stacked query slot within the context
+    const long t0 = t, tiles_c = (ctx_q[c] + QS - 1) / QS;
+    for (long i = 0; i < tiles_c; ++i, ++t) {
+      int32_t* te = tiles + t * TILE_INTS;
+      te[0] = 0; te[1] = d->cu_context[c]; te[2] = clen; te[3] = (int32_t)pt; te[4] = ctx_split[c];
+      te[5] = (int32_t)(std::min((long)QS, ctx_q[c] - i * QS) * G); te[6] = te[7] = 0;
+      for (int s = 0; s < ctx_split[c]; ++s, ++pt) {
+        int32_t* pe = parts + pt * PART_INTS;
+        pe[0] = (int32_t)t; pe[1] = s * ctx_chunk[c]; pe[2] = std::min(clen, (s + 1) * ctx_chunk[c]); pe[3] = 0;
+      }
+    }
+    for (int s = 0; s < d->n_seqs; ++s) {
+      if (d->context_index[s] != c) continue;
+      const int len = d->cu_seqlens[s + 1] - d->cu_seqlens[s];
+      const int sq0 = d->cu_seqlens_q ? d->cu_seqlens_q[s] : d->cu_seqlens[s];
+      const int lq = d->cu_seqlens_q ? d->cu_seqlens_q[s + 1] - sq0 : len;
+      for (int i = 0; i < lq; ++i, ++j) {
+        rowq[(t0 + j / QS) * QS + j % QS] = sq0 + i;
+        qinfo[2 * (long)(sq0 + i)] = (int32_t)((t0 + j / QS) * QS + j % QS);
+      }
+    }
+  }
+  for (int s = 0; s < d->n_seqs; ++s) {
+    const int s0 = d->cu_seqlens[s], len = d->cu_seqlens[s + 1] - s0;
+    const int sq0 = d->cu_seqlens_q ? d->cu_seqlens_q[s] : s0;
+    const int lq = d->cu_seqlens_q ? d->cu_seqlens_q[s + 1] - sq0 : len;
+    const int qsh = len - lq;            // local query i sits at own key position qsh + i
+    for (int q0 = 0; q0 < lq; q0 += QS, ++t, ++pt) {
+      const int nq = std::min(QS, lq - q0);
+      int32_t* te = tiles + t * TILE_INTS;
+      te[0] = 1; te[1] = s0; te[2] = len; te[3] = (int32_t)pt; te[4] = 1; te[5] = nq * G; te[6] = te[7] = 0;
+      int32_t* pe = parts + pt * PART_INTS;
+      pe[0] = (int32_t)t; pe[1] = 0; pe[2] = std::min(len, qsh + q0 + nq); pe[3] = 0;
+      for (int i = 0; i < nq; ++i) {
+        rowq[t * QS + i] = sq0 + q0 + i;
+        rowpos[t * QS + i] = qsh + q0 + i;
+        qinfo[2 * (long)(sq0 + q0 + i) + 1] = (int32_t)(t * QS + i);
+      }
+    }
+  }
+  return MJV_OK;
+}
+
+}  // namespace cx
+}  // namespace
+
+extern "C" int64_t mjv_attention_ctx_plan(const mjv_attn_ctx_desc* d, int32_t* plan_host, int64_t plan_ints) {
+  cx::PlanInfo info;
+  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  if (rc != MJV_OK) return rc;
+  if (!plan_host) return info.ints;
+  if (plan_ints < info.ints) {
+    mjv_set_error("attention_ctx_plan: the plan needs %ld ints, the buffer holds %ld", (long)info.ints, (long)plan_ints);
+    return MJV_E_ARG;
+  }
+  const int rc2 = cx::ctx_plan_build(d, plan_host, &info);
+  return rc2 != MJV_OK ? rc2 : info.ints;
+}
+
+extern "C" int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d) {
+  cx::PlanInfo info;
+  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  return rc != MJV_OK ? rc : info.ws_bytes;
+}
+
+extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) {
+  MJV_REQUIRE(d && d->Q && d->K && d->V && d->O && d->ctx_k && d->ctx_v, "attention_ctx: null pointer");
+  if (!d->causal) {
+    mjv_set_error("attention_ctx: only causal launches are built (a sequence's own rows follow its context)");
+    return MJV_E_UNSUPPORTED;
+  }
+  MJV_REQUIRE(d->score_round_mode == 1 || d->score_round_mode == 2, "attention_ctx: score_round_mode %d not in {1, 2}", d->score_round_mode);
+  cx::PlanInfo info;
+  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  if (rc != MJV_OK) return rc;
+  MJV_REQUIRE(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 8 == 0 && d->ld_ctx_k % 8 == 0 && d->ld_ctx_v % 8 == 0,
+              "attention_ctx: ld alignment (multiples of 8 elements)");
+  MJV_REQUIRE(d->q_head_stride % 8 == 0 && d->k_head_stride % 8 == 0 && d->v_head_stride % 8 == 0 && d->o_head_stride % 8 == 0 &&
+                  d->ctx_k_head_stride % 8 == 0 && d->ctx_v_head_stride % 8 == 0, "attention_ctx: head stride alignment (multiples of 8 elements)");
+  MJV_REQUIRE(((uintptr_t)d->Q | (uintptr_t)d->K | (uintptr_t)d->V | (uintptr_t)d->O | (uintptr_t)d->ctx_k | (uintptr_t)d->ctx_v) % 16 == 0,
+              "attention_ctx: misaligned pointer (Q, K, V, O, ctx_k, ctx_v must be 16-byte aligned)");
+  MJV_REQUIRE(d->plan && d->plan_ints >= info.ints, "attention_ctx: missing or short plan (%ld ints given, %ld needed: mjv_attention_ctx_plan)",
+              (long)(d->plan ? d->plan_ints : 0), (long)info.ints);
+  MJV_REQUIRE(d->workspace && d->workspace_bytes >= info.ws_bytes && (uintptr_t)d->workspace % 16 == 0,
+              "attention_ctx: missing, misaligned or short workspace (%ld bytes given, %ld needed: mjv_attention_ctx_workspace_bytes)",
+              (long)(d->workspace ? d->workspace_bytes : 0), (long)info.ws_bytes);
+  cx::CtxArgs a;
+  a.Q = d->Q; a.K = d->K; a.V = d->V; a.O = d->O;
+  a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv; a.ldo = d->ldo;
+  a.qhs = d->q_head_stride; a.khs = d->k_head_stride; a.vhs = d->v_head_stride; a.ohs = d->o_head_stride;
+  a.Kc = d->ctx_k; a.Vc = d->ctx_v; a.ldkc = d->ld_ctx_k; a.ldvc = d->ld_ctx_v; a.kchs = d->ctx_k_head_stride; a.vchs = d->ctx_v_head_stride;
+  a.plan = d->plan;
+  a.G = d->kv_group; a.n_heads = d->n_heads; a.n_kv = d->n_heads / d->kv_group;
+  a.n_parts = (int)info.n_parts; a.n_tiles = (int)info.n_tiles; a.total_q = (int)info.total_q;
+  a.scale = d->scale;
+  const long slabs = info.n_parts * a.n_kv;
+  a.ws_ml = (float*)d->workspace;
+  a.ws_acc = (float*)d->workspace + slabs * cx::TR * 2;
+  hipStream_t s = (hipStream_t)stream;
+  MjvProfScope ps("attn_ctx_d128", s, 4.0 * d->head_dim * info.pairs * d->n_heads, 0);
+  if (d->score_round_mode == 2) hipLaunchKernelGGL((cx::attn_ctx_kernel<128, RM_FLASH>), dim3((unsigned)slabs), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((cx::attn_ctx_kernel<128, RM_DIV>), dim3((unsigned)slabs), dim3(256), 0, s, a);
+  const int rc2 = mjv_check_launch("attention_ctx");
+  if (rc2 != MJV_OK) return rc2;
+  const long pairs = info.total_q * d->n_heads;
+  hipLaunchKernelGGL((cx::attn_ctx_combine_kernel<128>), dim3((unsigned)((pairs + 7) / 8)), dim3(256), 0, s, a);
+  return mjv_check_launch("attention_ctx combine");
 }

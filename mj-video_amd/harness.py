@@ -147,6 +147,48 @@ def score_pair_batch(model, config, tokenizer, examples: Sequence[dict], generat
     return model.last_packed34.view(len(examples), 2, -1)
 
 
+@torch.no_grad()
+def score_video_captions(model, config, tokenizer, pixels: torch.Tensor, captions: Sequence[str], generation_config: dict) -> torch.Tensor:
+    """ONE video ([F, 3, S, S]) under M captions: the video goes through the vision tower and the context part of the
+    language tower once (``model.encode_video``), every caption as its own rows only (``model.score_captions``).
+    Returns ``[M, 1 + n_aspects + n_objectives]`` fp32 - the rows ``model.forward`` gives for the M full prompts, up to fp32
+    summation order."""
+    return score_caption_matrix(model, config, tokenizer, [pixels], captions, generation_config)[0]
+
+
+@torch.no_grad()
+def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor], captions: Sequence[str], generation_config: dict,
+                         max_rows: int = 64) -> torch.Tensor:
+    """V videos x M captions (caption-vs-distractor matrices, perturbed captions, re-caption choice): every video is encoded
+    once, the V * M caption rows go through ``model.score_captions`` in as few calls as ``max_rows`` rows per call allow.
+    Returns ``[V, M, 1 + n_aspects + n_objectives]`` fp32."""
+    _lib.assert_product_library()
+    if max_rows < 1:
+        raise ValueError("max_rows must be positive")
+    dev = model.model.device
+    pad_id = model.config.pad_token_id
+    if pad_id is None:
+        raise ValueError("model.config.pad_token_id must be set to batch captions (eval_genai_mjvideo.py:112)")
+    V, M = len(videos), len(captions)
+    if not V or not M:
+        raise ValueError("score_caption_matrix needs at least one video and one caption")
+    ids, contexts = [], []
+    for pv in videos:
+        pv = pv.to(torch.bfloat16)
+        rows = [prepare_chat_input(config, tokenizer, pv, video_prefix(pv.shape[0]) + c, generation_config, device="cpu")[0] for c in captions]
+        ids.extend(rows)
+        contexts.append(model.encode_video(pv.to(dev), rows[0]))
+    out = []
+    for lo in range(0, V * M, max_rows):
+        hi = min(V * M, lo + max_rows)
+        v0, v1 = lo // M, (hi - 1) // M
+        ids_b, mask = pad_right(ids[lo:hi], pad_id)
+        index = torch.tensor([r // M - v0 for r in range(lo, hi)], dtype=torch.int64)
+        model.score_captions(contexts[v0:v1 + 1], ids_b.to(dev), mask.to(dev), context_index=index)
+        out.append(model.last_packed34)
+    return torch.cat(out).view(V, M, -1)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Collator batch format and MJ-BENCH-VIDEO label schema (SURVEY.md §8(f) items 2-3)
 @torch.no_grad()

@@ -88,6 +88,29 @@ class CustomOutput:
         return [f.name for f in fields(self) if getattr(self, f.name) is not None]
 
 
+class VideoContext:
+    """What ``model.encode_video`` keeps of ONE video for ``model.score_captions``: the language tower's rotated keys and values
+    of the prompt's first ``P`` tokens (system tokens + frame labels + image tokens) in every decoder layer, compact
+    (``k[layer]`` / ``v[layer]``: [P, kv_heads * head_dim] bf16 each), and the projected image embeddings of the few video rows
+    behind ``P`` (``img_tail``: they are re-spliced into every caption's own rows).
+    Size: 2 * P * kv_heads * head_dim * 2 bytes per layer - MJ-VIDEO-2B (24 layers, 8 kv heads of 128) at P = 2 112
+    (8 frames @448^2): 8.65 MB per layer, 207.6 MB per video (``nbytes``); the whole wqkv rows ``_build_prefix`` clones for its 64
+    system tokens would be 415 MB at this length.
+    Valid for the model state it was built under (``settings``: weights as ``_prepare`` tracks them, rotary base, attention
+    numerics, FFN format, norm fusion, device): ``score_captions`` refuses it under any other and never rebuilds it."""
+
+    def __init__(self, ids, P, k, v, img_tail, tail_cols, n_img, settings, ready, stream, device):
+        self.ids, self.P, self.k, self.v, self.img_tail, self.tail_cols, self.n_img = ids, P, k, v, img_tail, tail_cols, n_img
+        self.settings, self.ready, self.stream, self.device = settings, ready, stream, device
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def tensors(self):
+        return self.k + self.v + [self.img_tail]
+
+
 # ------------------------------------------------------------------------------- parameter holders
 class _Linear(nn.Module):
     def __init__(self, fin: int, fout: int, bias: bool = True):
@@ -501,6 +524,10 @@ class InternVLChatRewardModeling(nn.Module):
         self._prefix_misses = 0      # consecutive forwards that found no cached prefix (see _forward_group: thrash guard)
         self._prefix_last_miss = None
         self.prefix_cache_hits = 0   # forwards served from the cache (tests / bench report)
+        # score_captions: "shared" = one mjv_attention_ctx_bf16 launch per layer for every context of the batch (the product);
+        # "per-context" = one launch of the existing kernel per context with prefix_k / prefix_v - its A/B partner and a
+        # cross-check (tools/caption_bench.py, tests), not a product mode
+        self.caption_attention = "shared"
 
     # -- construction helpers -------------------------------------------------------------------
     @classmethod
@@ -1091,8 +1118,9 @@ class InternVLChatRewardModeling(nn.Module):
         (moe_reward.py:211,229,243) - and the [len(sel_rows), hidden] result is returned instead of ``x``.
         ``tail`` (with ``sel_rows``; ``trim_last_layer``) = (tail_rows, tail_pos, cu_tail, max_tail, sel_in_tail): the last
         layer computes queries only for those rows.  ``prefix`` = the cached keys / values of the prompt prefix the packed rows
-        leave out (``prefix_cache``); ``snapshot`` (the prefix-only pass of ``_build_prefix``) = (P, store): keep rows [0, P) of
-        every layer's K / V in ``store``."""
+        leave out (``prefix_cache``); ``snapshot`` (the prefix-only pass of ``_build_prefix``, the context pass of ``encode_video``) =
+        (P, store): keep rows [0, P) of every layer's K / V in ``store["k"]`` / ``store["v"]`` - the values as the layer's whole
+        wqkv rows, or, with ``store["compact_values"]`` set, as the value heads alone ([P, kv heads * 128])."""
         dev = x.device
         lc = self.config.llm_config
         lm = self.model.language_model.model
@@ -1206,7 +1234,11 @@ class InternVLChatRewardModeling(nn.Module):
                 ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G))
             if snapshot is not None and not phi3:   # the prompt prefix's keys (rotated) and values of this layer
                 snapshot[1]["k"].append(k[:snapshot[0]].clone())
-                snapshot[1]["v"].append(qkv[:snapshot[0]].clone())
+                if snapshot[1].get("compact_values"):   # (encode_video) the value heads alone: [P, kv heads * 128]
+                    snapshot[1]["v"].append(qkv[:snapshot[0]].view(snapshot[0], KV, G + 2, hd)[:, :, G + 1]
+                                            .clone(memory_format=torch.contiguous_format).view(snapshot[0], KV * hd))
+                else:
+                    snapshot[1]["v"].append(qkv[:snapshot[0]].clone())
             if not phi3:
                 ops.attention(q, k, v_view, hn, cu, max_len, H, G, hd, True, scale, mode, v_head_stride=(G + 2) * hd,
                               prefix_k=pk, prefix_v=(prefix["v"][li][:, (G + 1) * hd:] if prefix is not None else None))
@@ -1447,6 +1479,344 @@ class InternVLChatRewardModeling(nn.Module):
             aspect_scores=torch.empty(B, nasp, dtype=torch.float32, device=dev),
             score=torch.empty(B, dtype=torch.float32, device=dev),
             packed34=torch.empty(B, 1 + nasp + nobj, dtype=torch.float32, device=dev))
+
+    # -- one cached video context, many captions ------------------------------------------------
+    def _caption_guard(self, dev):
+        if dev.type != "cuda":
+            raise RuntimeError("encode_video / score_captions run on the MI355X only: move the model with .cuda()")
+        if self._phi3:
+            raise NotImplementedError("encode_video / score_captions are built for the InternLM2 tower (head_dim 128) only")
+        if self.norm_fusion or self._exp8_set() or self.debug_probes is not None:
+            raise NotImplementedError("encode_video / score_captions: norm_fusion, the fp8 attention-side study and debug_probes "
+                                      "are not built into the caption pass")
+        if self.model.img_context_token_id is None:
+            raise ValueError("model.model.img_context_token_id is not set (eval_genai_mjvideo.py:115)")
+
+    def _caption_settings(self, padded_len: int, dev):
+        """what a VideoContext's keys / values depend on besides its token ids - the tuple ``_forward_group`` builds for the
+        system-prefix cache, without the last layer's buffer form (a context keeps compact rows of its own)"""
+        return (self._derived_sig, self._rope_next_state(int(padded_len))["base"], self.attention_scores, self.ffn_format,
+                bool(self.norm_fusion), self._exp8_set(), bool(self.use_gemm_workspace), str(dev))
+
+    @torch.no_grad()
+    def encode_video(self, pixel_values: torch.Tensor, input_ids: torch.Tensor,
+                     attention_mask: Optional[torch.Tensor] = None) -> VideoContext:
+        """The part of a scoring forward that does not depend on the caption, once per video: the vision tower on
+        ``pixel_values`` [tiles, 3, S, S] (bf16), then the language tower over the first ``P`` tokens of ``input_ids`` ALONE
+        (one full prompt of that video, [N] or [1, N]; what follows the video tokens is ignored), keeping every layer's
+        rotated keys and its values compact.  ``P`` = the column after the last <IMG_CONTEXT>, cut down to a multiple of 64
+        (the attention kernels' key-tile rule): 2 112 at 8 x 256 image tokens with the synthetic prompt, 576 @224^2.  The
+        projected embeddings of image tokens behind ``P`` (7 in that example) stay in the context and are re-spliced per
+        caption.  207.6 MB per video for MJ-VIDEO-2B at P = 2 112 (``VideoContext.nbytes``)."""
+        dev = self.model.device
+        self._caption_guard(dev)
+        if pixel_values.dim() != 4:
+            raise ValueError(f"wrong pixel_values size: {tuple(pixel_values.shape)}")
+        if pixel_values.dtype != BF16:
+            raise TypeError(f"pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
+        ids = input_ids.detach().to("cpu").numpy()
+        if ids.ndim == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.ndim != 1:
+            raise ValueError(f"encode_video takes ONE prompt ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
+        N = int(ids.shape[0])
+        d = self._prepare(dev)
+        ctx_id = self.model.img_context_token_id
+        cols = np.flatnonzero(ids == ctx_id)
+        tiles = int(pixel_values.shape[0])
+        n_img = tiles * self.model.num_image_token
+        if cols.size != n_img or n_img == 0:
+            raise ValueError(f"{cols.size} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {tiles} tiles x "
+                             f"{self.model.num_image_token} image tokens")
+        P = ((int(cols[-1]) + 1) // 64) * 64
+        if P <= 0:
+            raise ValueError(f"the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
+        if attention_mask is not None:
+            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
+            if am.shape[0] != N or not am[:P].all():
+                raise ValueError(f"attention_mask must cover the prompt and be set on all of its first {P} (context) columns")
+        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
+        if int(ids[:P].min()) < 0 or int(ids[:P].max()) >= vocab:
+            raise IndexError(f"token id out of range [0, {vocab})")
+        n_in = int((cols < P).sum())
+        lc = self.config.llm_config
+        hdim = lc.hidden_size
+        settings = self._caption_settings(N, dev)
+        pixel_values = pixel_values.to(dev).contiguous()
+        try:
+            with torch.cuda.device(dev):
+                self._ws_tag = "g0"
+                ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
+                                       if self.use_gemm_workspace else None)
+                ph, _ = self._vision_tower_launch(d, pixel_values)
+                x = self._buf("llm_x", P, hdim, dev)
+                def up(a):   # through pinned memory: the host does not wait for what the stream is still running
+                    pin = torch.empty(a.shape, dtype=torch.int32, pin_memory=True)
+                    pin.numpy()[...] = a
+                    return pin.to(dev, non_blocking=True)
+
+                ops.embed_gather(up(ids[:P]), self.model.language_model.model.tok_embeddings.weight, x, ctx_id)
+                mlp1 = self.model.mlp1
+                if n_in:
+                    ops.gemm(ph[:n_in], mlp1[3].weight, x, EPI_BIAS, bias=mlp1[3].bias,
+                             out_rows=up(cols[:n_in]))
+                img_tail = torch.empty(n_img - n_in, hdim, dtype=BF16, device=dev)
+                if n_img > n_in:
+                    ops.gemm(ph[n_in:n_img], mlp1[3].weight, img_tail, EPI_BIAS, bias=mlp1[3].bias)
+                cu = up(np.asarray([0, P]))
+                pos = torch.arange(P, dtype=torch.int32, device=dev)
+                store = dict(k=[], v=[], compact_values=True)
+                self._language_tower(d, x, cu, pos, P, None, padded_len=N, snapshot=(P, store))
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(dev))
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        finally:
+            ops.set_gemm_workspace(None)
+        return VideoContext(ids[:P].copy(), P, store["k"], store["v"], img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
+
+    def _analyse_captions(self, ids: np.ndarray, am: Optional[np.ndarray], ctxs, ci: np.ndarray, group: bool):
+        """Validates every caption row against its context (nothing is repaired) and derives the packed own rows: what
+        ``_analyse_ids`` derives for whole prompts, for the columns behind each row's context.  ``group``: pack the sequences
+        context by context (the "per-context" launches address a context's sequences as one range)."""
+        M, N = ids.shape
+        pad_id = self.config.pad_token_id
+        if pad_id is None and M != 1:
+            raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
+        ctx_id = self.model.img_context_token_id
+        if am is not None:
+            if am.shape != ids.shape:
+                raise ValueError(f"attention_mask shape {am.shape} != input_ids shape {ids.shape}")
+            am = am.astype(bool)
+        else:
+            am = np.ones((M, N), dtype=bool)
+        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
+        valid = ids[am]
+        if valid.size and (int(valid.min()) < 0 or int(valid.max()) >= vocab):
+            raise IndexError(f"token id out of range [0, {vocab}): min {int(valid.min())}, max {int(valid.max())}")
+        toff = np.concatenate([[0], np.cumsum([c.tail_cols.size for c in ctxs])])
+        rs, gs, own_cols, img_src = [], [], [], []
+        for b in range(M):
+            row, c = ids[b], ctxs[int(ci[b])]
+            P = c.P
+            if N < P:
+                raise ValueError(f"row {b}: {N} columns, its context {int(ci[b])} holds {P} tokens")
+            differ = np.flatnonzero(row[:P] != c.ids)
+            if differ.size:
+                raise ValueError(f"row {b}: its first {P} token ids differ from those of its context {int(ci[b])} "
+                                 f"(first at column {int(differ[0])})")
+            if not am[b, :P].all():
+                raise ValueError(f"row {b}: masked column {int(np.flatnonzero(~am[b, :P])[0])} inside its context ({P} tokens)")
+            r = N - 1 if pad_id is None else (int(np.argmax(row == pad_id)) - 1) % N
+            g = find_token_for_gating(row, getattr(self.config, "gating_token_pattern", None))
+            if r < P or g < P:
+                raise ValueError(f"row {b}: reward row {r} / gating row {g} lies inside its context ({P} tokens)")
+            if not am[b, r] or not am[b, g]:
+                raise ValueError(f"row {b}: reward row {r} / gating row {g} lies in the masked part of the sequence")
+            ic = np.flatnonzero(row == ctx_id)
+            if ic.size != c.n_img:
+                raise ValueError(f"row {b}: {ic.size} <IMG_CONTEXT> tokens, its context {int(ci[b])} was built from {c.n_img}")
+            if not am[b, ic].all():
+                raise ValueError(f"row {b}: <IMG_CONTEXT> tokens in the masked part of the sequence")
+            cols = P + np.flatnonzero(am[b, P:])
+            src = np.full(cols.shape[0], -1, dtype=np.int32)       # row of the contexts' image-tail table, or -1
+            tail = ic[ic >= P]
+            src[np.searchsorted(cols, tail)] = toff[int(ci[b])] + np.arange(tail.size)
+            rs.append(r)
+            gs.append(g)
+            own_cols.append(cols)
+            img_src.append(src)
+        order = np.argsort(ci, kind="stable") if group else np.arange(M)
+        cu, cu_tail = [0], [0]
+        reward_rows, gating_rows = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        sel_r, sel_g = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
+        tail_rows, tail_pos = [], []
+        for b in order:
+            cols = own_cols[b]
+            base, L = cu[-1], cols.shape[0]
+            lr, lg = int(np.searchsorted(cols, rs[b])), int(np.searchsorted(cols, gs[b]))
+            reward_rows[b], gating_rows[b] = base + lr, base + lg
+            t0 = min(lr, lg)
+            tb = cu_tail[-1] - t0
+            tail_rows.append(base + np.arange(t0, L))
+            tail_pos.append(cols[t0:])
+            sel_r[b], sel_g[b] = tb + lr, tb + lg
+            cu.append(base + L)
+            cu_tail.append(tb + L)
+        return dict(M=M, N=N, total=cu[-1], order=order, index=ci[order].astype(np.int32),
+                    ids=np.concatenate([ids[b][own_cols[b]] for b in order]).astype(np.int32),
+                    positions=np.concatenate([own_cols[b] for b in order]).astype(np.int32),
+                    img_src=np.concatenate([img_src[b] for b in order]).astype(np.int32),
+                    cu=np.asarray(cu, dtype=np.int32), sel_rows=np.concatenate([reward_rows, gating_rows]),
+                    tail_rows=np.concatenate(tail_rows).astype(np.int32), tail_pos=np.concatenate(tail_pos).astype(np.int32),
+                    cu_tail=np.asarray(cu_tail, dtype=np.int32), sel_in_tail=np.concatenate([sel_r, sel_g]))
+
+    def _caption_tower(self, d, x: torch.Tensor, info, ctxs, dev):
+        """The decoder layers on the captions' own rows ``x`` (in place), every row attending to [its context | the own rows
+        before it]; the last layer as ``_language_tower`` runs it for a scorer.  Returns the [2 M, hidden] selected rows."""
+        lc = self.config.llm_config
+        lm = self.model.language_model.model
+        H, KV = lc.num_attention_heads, lc.num_key_value_heads
+        G, hd = H // KV, lc.hidden_size // lc.num_attention_heads
+        n, hdim = x.shape
+        ff = lc.intermediate_size
+
+        def up(a):
+            return torch.from_numpy(a).to(dev, non_blocking=True)
+
+        cos, sin = self._rope_tables(info["N"], dev)
+        positions, sel_rows = up(info["positions"]), up(info["sel_rows"])
+        trim = bool(self.trim_last_layer)
+        shared = self.caption_attention == "shared"
+        cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
+        lens, lens_t = np.diff(info["cu"]), np.diff(info["cu_tail"])
+        if shared:
+            plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev)
+            plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"]) if trim else None
+            ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
+                           dtype=torch.uint8).view(-1)
+        else:
+            cu_d, cu_tail_d = up(info["cu"]), up(info["cu_tail"])
+            # sequences [lo, hi) of every context that has any (packed context by context)
+            ranges = [(c, int(np.searchsorted(info["index"], c, "left")), int(np.searchsorted(info["index"], c, "right")))
+                      for c in range(len(ctxs))]
+            ranges = [r for r in ranges if r[2] > r[1]]
+            vc = self._buf("cap_v", n, KV * hd, dev)
+        hn = self._buf("llm_hn", n, hdim, dev)
+        qkv = self._buf("llm_qkv", n, (H + 2 * KV) * hd, dev)
+        q = self._buf("llm_q", n, H * hd, dev)
+        k = self._buf("llm_k", n, KV * hd, dev)
+        act = self._buf("llm_act", n, ff, dev)
+        scale = 1.0 / math.sqrt(hd)
+        mode = 2 if self.attention_scores == "flash" else 1
+        P_all = int(cu_ctx[-1])
+
+        def attend(li, qq, v, vhs, out, tail: bool):
+            if shared:
+                if len(ctxs) == 1:
+                    ck, cv = ctxs[0].k[li], ctxs[0].v[li]
+                else:   # the kernel takes the contexts' rows as ONE packed buffer: gathered per layer
+                    ck, cv = self._buf("cap_ctx_k", P_all, KV * hd, dev), self._buf("cap_ctx_v", P_all, KV * hd, dev)
+                    torch.cat([c.k[li] for c in ctxs], out=ck)
+                    torch.cat([c.v[li] for c in ctxs], out=cv)
+                ops.attention_ctx(qq, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=vhs)
+                return
+            # A/B partner: the existing kernel, one launch per context; its prefix rows share the live rows' layout: compact values
+            vc.view(n, KV, hd).copy_(torch.as_strided(v, (n, KV, hd), (v.stride(0), vhs, 1)))
+            for c, lo, hi in ranges:
+                ops.attention(qq, k, vc, out, cu_d[lo:hi + 1], int(lens[lo:hi].max()), H, G, hd, True, scale, mode,
+                              cu_seqlens_q=cu_tail_d[lo:hi + 1] if tail else None, max_seqlen_q=int(lens_t[lo:hi].max()) if tail else 0,
+                              prefix_k=ctxs[c].k[li], prefix_v=ctxs[c].v[li])
+
+        def selected(li, layer, att, att_index):
+            ns = sel_rows.numel()
+            att_s = self._buf("llm_att_sel", ns, hdim, dev)
+            x_s = self._buf("llm_x_sel", ns, hdim, dev)
+            hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
+            act_s = self._buf("llm_act_sel", ns, ff, dev)
+            ops.embed_gather(att_index, att, att_s, -1)
+            ops.embed_gather(sel_rows, x, x_s, -1)
+            ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
+            self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
+            return x_s
+
+        last = len(lm.layers) - 1
+        for li, layer in enumerate(lm.layers):
+            ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
+            if li == last and trim:
+                # queries only from the first selected row on (trim_last_layer, as _language_tower): k | v of every own row, the
+                # whole wqkv on the tail rows
+                tail_rows, tail_pos = up(info["tail_rows"]), up(info["tail_pos"])
+                nt = tail_rows.numel()
+                kv = self._buf("llm_kv_last", n, 2 * KV * hd, dev)
+                ops.gemm(hn, d["wkv_last"], kv, EPI_ROPE_QKV, rope=(cos, sin, positions, None, k, 0))
+                hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
+                qkv_t = self._buf("llm_qkv_tail", nt, (H + 2 * KV) * hd, dev)
+                q_t = self._buf("llm_q_tail", nt, H * hd, dev)
+                k_t = self._buf("llm_k_tail", nt, KV * hd, dev)
+                att_t = self._buf("llm_att_tail", nt, H * hd, dev)
+                ops.embed_gather(tail_rows, hn, hn_t, -1)
+                ops.gemm(hn_t, layer.attention.wqkv.weight, qkv_t, EPI_ROPE_QKV, rope=(cos, sin, tail_pos, q_t, k_t, G))
+                attend(li, q_t, kv[:, hd:], 2 * hd, att_t, True)
+                return selected(li, layer, att_t, up(info["sel_in_tail"]))
+            ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G))
+            attend(li, q, qkv[:, (G + 1) * hd:], (G + 2) * hd, hn, False)
+            if li == last:
+                return selected(li, layer, hn, sel_rows)
+            ops.gemm(hn, layer.attention.wo.weight, x, EPI_SCALE_RES, res=x)
+            self._llm_ffn(d, li, layer, x, hn, act, "all")
+        raise AssertionError("unreachable")
+
+    @torch.no_grad()
+    def score_captions(self, contexts, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                       context_index=None) -> CustomOutput:
+        """Scores M full prompts ``input_ids`` [M, N] (right-padded; ``attention_mask`` as in ``forward``) whose video part is
+        already encoded: row i belongs to ``contexts[context_index[i]]`` (one ``VideoContext`` or a list; default: all rows to
+        context 0) and only its columns behind that context go through the language tower - no vision tower, no context rows in
+        any GEMM; every layer's attention reads the context's cached keys / values (``caption_attention``).  Same nine
+        ``CustomOutput`` fields as ``forward``, ``last_packed34`` set.  ``ValueError`` (naming the row, nothing is repaired) for a
+        row whose first P ids differ from its context's, a masked column or a reward / gating row inside the context, another
+        <IMG_CONTEXT> count than the context was built from, and for a context built under other settings than the model has
+        now (new weights, another ``attention_scores`` / FFN format, a rotary base dynamic NTK has moved since) or on another
+        device.  A context is never rebuilt here."""
+        dev = self.model.device
+        self._caption_guard(dev)
+        ctxs = [contexts] if isinstance(contexts, VideoContext) else list(contexts)
+        if not ctxs or not all(isinstance(c, VideoContext) for c in ctxs):
+            raise ValueError("score_captions: contexts must be a VideoContext or a non-empty list of them (model.encode_video)")
+        if self.caption_attention not in ("shared", "per-context"):
+            raise ValueError(f"caption_attention {self.caption_attention!r} not in ('shared', 'per-context')")
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [captions, seq], got {tuple(input_ids.shape)}")
+        d = self._prepare(dev)
+        M, N = int(input_ids.shape[0]), int(input_ids.shape[1])
+        if context_index is None:
+            ci = np.zeros(M, dtype=np.int64)
+        else:
+            ci = (context_index.detach().to("cpu").numpy() if isinstance(context_index, torch.Tensor) else np.asarray(context_index))
+            ci = ci.astype(np.int64).reshape(-1)
+            if ci.shape[0] != M:
+                raise ValueError(f"context_index names {ci.shape[0]} rows, input_ids has {M}")
+            bad = np.flatnonzero((ci < 0) | (ci >= len(ctxs)))
+            if bad.size:
+                raise ValueError(f"row {int(bad[0])}: context_index {int(ci[bad[0]])} out of range ({len(ctxs)} contexts)")
+        settings = self._caption_settings(N, dev)
+        for c, ctx in enumerate(ctxs):
+            if ctx.device != dev:
+                raise ValueError(f"context {c} lives on {ctx.device}, the model on {dev}")
+            if ctx.settings != settings:
+                raise ValueError(f"context {c} was built under other settings than the model has now (weights, rotary base, "
+                                 "attention_scores, FFN format or device changed since encode_video): encode the video again")
+        ids, am = self._host_ids(input_ids, attention_mask)
+        info = self._analyse_captions(ids, am, ctxs, ci, group=self.caption_attention == "per-context")
+        outs = self._alloc_outputs(M, dev)
+        lc = self.config.llm_config
+        try:
+            with torch.cuda.device(dev):
+                self._ws_tag = "g0"
+                ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
+                                       if self.use_gemm_workspace else None)
+                cur = torch.cuda.current_stream(dev)
+                for ctx in ctxs:   # built on another stream: wait for the rows, and tell the allocator who reads them
+                    if ctx.stream != cur.cuda_stream:
+                        cur.wait_event(ctx.ready)
+                        for t in ctx.tensors():
+                            t.record_stream(cur)
+                hidden = self._buf("llm_x", info["total"], lc.hidden_size, dev)
+                ops.embed_gather(torch.from_numpy(info["ids"]).to(dev, non_blocking=True),
+                                 self.model.language_model.model.tok_embeddings.weight, hidden, self.model.img_context_token_id)
+                if (info["img_src"] >= 0).any():   # the image tokens behind the contexts' boundary: their cached embeddings
+                    table = ctxs[0].img_tail if len(ctxs) == 1 else torch.cat([c.img_tail for c in ctxs])
+                    ops.embed_gather(torch.from_numpy(info["img_src"]).to(dev, non_blocking=True), table, hidden, -1)
+                last_x = self._caption_tower(d, hidden, info, ctxs, dev)
+                h_r, h_g = outs["hidden_state"], outs["prompt_embedding"]
+                norm_w = self.model.language_model.model.norm.weight
+                ops.rmsnorm(last_x[:M], norm_w, h_r, lc.rms_norm_eps)
+                ops.rmsnorm(last_x[M:], norm_w, h_g, lc.rms_norm_eps)
+                self._run_heads(d, h_r, h_g, outs, 0, M, dev)
+        finally:
+            ops.set_gemm_workspace(None)
+        self.last_packed34 = outs.pop("packed34")
+        return CustomOutput(**outs)
 
     @torch.no_grad()
     def heads_forward(self, hidden_state: torch.Tensor, prompt_embedding: torch.Tensor) -> CustomOutput:

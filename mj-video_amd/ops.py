@@ -13,8 +13,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_ROPE_QKV, EPI_SCALE_RES, EPI_SILU_MUL, FMT_MXFP8, AttnDesc,
-                   GemmDesc, HeadsDesc, check, load_library)
+from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_ROPE_QKV, EPI_SCALE_RES, EPI_SILU_MUL, FMT_MXFP8, AttnCtxDesc,
+                   AttnDesc, GemmDesc, HeadsDesc, check, load_library)
 
 BF16 = torch.bfloat16
 
@@ -258,6 +258,75 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
         d.prefix_k, d.prefix_v, d.prefix_len = prefix_k.data_ptr(), prefix_v.data_ptr(), prefix_k.shape[0]
     with torch.cuda.device(out.device):
         check(lib.mjv_attention_bf16(C.byref(d), _stream(out)), "mjv_attention_bf16")
+    return out
+
+
+class AttnCtxPlan:
+    """What one batch of the caption pass needs for ``attention_ctx`` (include/mjv.h, mjv_attn_ctx_desc): the HOST index arrays
+    (kept alive here: the C entry reads them in every call), the device copy of the plan ``mjv_attention_ctx_plan`` derived from
+    them, and the size of the fp32 partials.  Built once per batch, used by every layer's launch."""
+
+    def __init__(self, cu_seqlens, context_index, cu_context, n_heads: int, kv_group: int, head_dim: int, device,
+                 cu_seqlens_q=None):
+        import numpy as np
+        as_i32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32))  # noqa: E731
+        self.cu, self.cu_q, self.index, self.cu_ctx = as_i32(cu_seqlens), as_i32(cu_seqlens_q), as_i32(context_index), as_i32(cu_context)
+        if self.cu.ndim != 1 or self.cu.size < 2 or self.index.shape != (self.cu.size - 1,) or self.cu_ctx.ndim != 1 or self.cu_ctx.size < 2 \
+                or (self.cu_q is not None and self.cu_q.shape != self.cu.shape):
+            raise ValueError("attention_ctx plan: cu_seqlens [n + 1], context_index [n], cu_context [contexts + 1], cu_seqlens_q [n + 1] or None")
+        self.n_heads, self.kv_group, self.head_dim, self.device = n_heads, kv_group, head_dim, torch.device(device)
+        lib = load_library()
+        d = self.desc()
+        n = lib.mjv_attention_ctx_plan(C.byref(d), None, 0)
+        if n < 0:
+            check(int(n), "mjv_attention_ctx_plan")
+        host = np.empty(int(n), dtype=np.int32)
+        check(min(0, int(lib.mjv_attention_ctx_plan(C.byref(d), host.ctypes.data, int(n)))), "mjv_attention_ctx_plan")
+        self.plan_ints = int(n)
+        self.workspace_bytes = int(lib.mjv_attention_ctx_workspace_bytes(C.byref(d)))
+        self.total_q = int((self.cu_q if self.cu_q is not None else self.cu)[-1])
+        self.plan = torch.from_numpy(host).to(self.device, non_blocking=False)
+
+    def desc(self) -> AttnCtxDesc:
+        d = AttnCtxDesc()
+        d.cu_seqlens, d.context_index, d.cu_context = self.cu.ctypes.data, self.index.ctypes.data, self.cu_ctx.ctypes.data
+        d.cu_seqlens_q = None if self.cu_q is None else self.cu_q.ctypes.data
+        d.n_seqs, d.n_contexts = self.cu.size - 1, self.cu_ctx.size - 1
+        d.n_heads, d.kv_group, d.head_dim, d.causal = self.n_heads, self.kv_group, self.head_dim, 1
+        return d
+
+
+def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, ctx_k: torch.Tensor, ctx_v: torch.Tensor,
+                  plan: AttnCtxPlan, scale: float, score_round_mode: int, workspace: Optional[torch.Tensor],
+                  q_head_stride: Optional[int] = None, k_head_stride: Optional[int] = None, v_head_stride: Optional[int] = None,
+                  o_head_stride: Optional[int] = None, ctx_k_head_stride: Optional[int] = None,
+                  ctx_v_head_stride: Optional[int] = None, causal: bool = True) -> torch.Tensor:
+    """Causal attention of every sequence's own rows (q / k / v / out: 2-D views as in ``attention``) over
+    [its context's rows of ``ctx_k`` / ``ctx_v`` | its own rows] (include/mjv.h, mjv_attention_ctx_bf16).  ``plan``: the batch's
+    ``AttnCtxPlan``; ``workspace``: a uint8 device tensor of at least ``plan.workspace_bytes`` (the library allocates nothing)."""
+    _chk_bf16(q, k, v, out, ctx_k, ctx_v)
+    hd = plan.head_dim
+    if q.shape[0] < plan.total_q or out.shape[0] < plan.total_q or k.shape[0] < int(plan.cu[-1]) or v.shape[0] < int(plan.cu[-1]) \
+            or ctx_k.shape[0] < int(plan.cu_ctx[-1]) or ctx_v.shape[0] < int(plan.cu_ctx[-1]):
+        raise ValueError("attention_ctx: a tensor holds fewer rows than the plan's index arrays address")
+    if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_cuda):
+        raise TypeError("attention_ctx: workspace must be a uint8 device tensor")
+    d = plan.desc()
+    d.Q, d.K, d.V, d.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    d.ldq, d.ldk, d.ldv, d.ldo = _row_stride(q), _row_stride(k), _row_stride(v), _row_stride(out)
+    d.q_head_stride = hd if q_head_stride is None else q_head_stride
+    d.k_head_stride = hd if k_head_stride is None else k_head_stride
+    d.v_head_stride = hd if v_head_stride is None else v_head_stride
+    d.o_head_stride = hd if o_head_stride is None else o_head_stride
+    d.ctx_k, d.ctx_v, d.ld_ctx_k, d.ld_ctx_v = ctx_k.data_ptr(), ctx_v.data_ptr(), _row_stride(ctx_k), _row_stride(ctx_v)
+    d.ctx_k_head_stride = hd if ctx_k_head_stride is None else ctx_k_head_stride
+    d.ctx_v_head_stride = hd if ctx_v_head_stride is None else ctx_v_head_stride
+    d.causal, d.scale, d.score_round_mode = int(causal), scale, score_round_mode
+    d.plan, d.plan_ints = plan.plan.data_ptr(), plan.plan_ints
+    if workspace is not None:
+        d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    with torch.cuda.device(out.device):
+        check(load_library().mjv_attention_ctx_bf16(C.byref(d), _stream(out)), "mjv_attention_ctx_bf16")
     return out
 
 

@@ -11,7 +11,7 @@ from mj_video_amd import InternVLChatRewardModelingConfig, prepare_chat_input  #
 
 
 def __getattr__(name):
-    if name in ("InternVLChatRewardModeling", "CustomOutput", "InternVLChatModel"):
+    if name in ("InternVLChatRewardModeling", "CustomOutput", "InternVLChatModel", "VideoContext"):
         import mj_video_amd.modeling as m
         return getattr(m, name)
     raise AttributeError(name)

@@ -1,0 +1,173 @@
+"""Many captions per video: ``encode_video`` + ``score_captions`` against ``forward`` on the same full prompts.
+
+    python tools/caption_bench.py [--m 1,2,4,8,16,64] [--reps 5] [--out FILE.json] [--matrix 8x8] [--size 448] [--frames 8]
+
+MJ-VIDEO-2B dims, random-init weights generated on the device (bench.py's), 8 frames @448^2, captions of 24 - 96 tokens.
+Per M: ms of ``encode_video``; ms of ``score_captions`` with caption_attention "shared" and "per-context" (alternated rep by rep
+in this one process); ms of ``forward`` on the M full prompts in batches of at most 8 videos (all the model could do before:
+the baseline); captions/s.  Every shape is warmed first; a timed region is bracketed by device events and ends in a
+synchronise.  Then the library profiler's per-tag table of one caption pass (attention share, small-GEMM share) and V x M
+through ``harness.score_caption_matrix``.  One JSON document on stdout (and in --out).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+from mj_video_amd import configuration as C, harness, ops, synth  # noqa: E402
+from mj_video_amd.chat_input import num_image_tokens_per_tile  # noqa: E402
+from mj_video_amd.modeling import InternVLChatRewardModeling  # noqa: E402
+
+
+class CharTokenizer:
+    """duck-typed tokenizer for the harness call: the special tokens are single ids, every other character one id"""
+    special = {"<|im_start|>": 92543, "<|im_end|>": 92542, "<img>": 92544, "</img>": 92545, "<IMG_CONTEXT>": 92546}
+
+    def convert_tokens_to_ids(self, t):
+        return self.special[t]
+
+    def __call__(self, text, return_tensors="pt"):
+        ids, i = [1], 0
+        while i < len(text):
+            for tok, tid in self.special.items():
+                if text.startswith(tok, i):
+                    ids.append(tid)
+                    i += len(tok)
+                    break
+            else:
+                if text.startswith("assistant", i):
+                    ids += [525, 11353]
+                    i += 9
+                else:
+                    ids.append(364 if text[i] == "\n" else 1000 + (ord(text[i]) % 50000))
+                    i += 1
+        t = torch.tensor([ids])
+        return {"input_ids": t, "attention_mask": torch.ones_like(t)}
+
+
+def timed(fn, reps):
+    """median / min ms of ``fn`` over ``reps`` runs, device events around work that ends in a synchronise"""
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return dict(median_ms=statistics.median(ms), min_ms=min(ms), reps=reps)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--m", default="1,2,4,8,16,64")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--size", type=int, default=448)
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--matrix", default="8x8")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    cfg = C.InternVLChatRewardModelingConfig(**C.mjvideo_2b_config_dict(args.size), **C.mjvideo_head_kwargs())
+    model = InternVLChatRewardModeling.from_config(cfg, dtype=torch.bfloat16, device=dev)
+    bench.random_init_on_device(model, cfg, dev, seed=0)
+    model.config.pad_token_id = synth.PAD_ID
+    model.model.img_context_token_id = synth.IMG_CONTEXT_ID
+    model.eval()
+    n_img = args.frames * num_image_tokens_per_tile(cfg)
+    px = synth.synth_pixel_values(7, 0, args.frames, args.size).to(dev)
+    doc = dict(config=f"MJ-VIDEO-2B dims, {args.frames} frames @{args.size}^2, captions of 24 - 96 tokens", device=torch.cuda.get_device_name(0),
+               rows=[])
+
+    def prompts_of(M):
+        return [synth.synth_input_ids(n_img, 900 + i, n_caption=24 + (i * 37) % 73) for i in range(M)]
+
+    def forward_all(ids, mask, M):
+        for lo in range(0, M, 8):
+            hi = min(M, lo + 8)
+            model.forward(px.repeat(hi - lo, 1, 1, 1), ids[lo:hi], mask[lo:hi])
+
+    for M in [int(x) for x in args.m.split(",")]:
+        prompts = prompts_of(M)
+        ids, mask = synth.pad_batch(prompts)
+        ids, mask = ids.to(dev), mask.to(dev)
+        ctx = model.encode_video(px, prompts[0])
+        for mode in ("shared", "per-context"):       # warm every shape
+            model.caption_attention = mode
+            model.score_captions(ctx, ids, mask)
+        forward_all(ids, mask, M)
+        torch.cuda.synchronize()
+        row = dict(M=M, context_tokens=ctx.P, context_bytes=ctx.nbytes, caption_rows=int(mask.sum().item()) - M * ctx.P)
+        row["encode_video"] = timed(lambda: model.encode_video(px, prompts[0]), args.reps)
+        res = {"shared": [], "per-context": []}
+        for _ in range(args.reps):                    # the two versions alternated within one process
+            for mode in ("shared", "per-context"):
+                model.caption_attention = mode
+                res[mode].append(timed(lambda: model.score_captions(ctx, ids, mask), 1)["median_ms"])
+        for mode, ms in res.items():
+            row[f"score_captions[{mode}]"] = dict(median_ms=statistics.median(ms), min_ms=min(ms), reps=len(ms))
+        model.caption_attention = "shared"
+        row["forward"] = timed(lambda: forward_all(ids, mask, M), max(2, args.reps // 2))
+        cap = row["score_captions[shared]"]["median_ms"]
+        row["captions_per_s"] = dict(encode_plus_shared=1e3 * M / (row["encode_video"]["median_ms"] + cap), shared_warm_context=1e3 * M / cap,
+                                     forward=1e3 * M / row["forward"]["median_ms"])
+        # the library profiler's per-tag table of ONE caption pass
+        ops.prof_enable(True)
+        ops.prof_reset()
+        model.score_captions(ctx, ids, mask)
+        tags = ops.prof_results()
+        ops.prof_enable(False)
+        ops.prof_reset()
+        total = sum(t["ms"] for t in tags.values())
+        row["caption_pass_tags"] = {k: dict(launches=t["launches"], ms=round(t["ms"], 4), share=round(t["ms"] / total, 4),
+                                            tflops=round(t["flops"] / t["ms"] / 1e9, 2) if t["ms"] > 0 else 0.0)
+                                    for k, t in sorted(tags.items(), key=lambda kv: -kv[1]["ms"])}
+        row["caption_pass_shares"] = dict(attention=round(sum(t["ms"] for k, t in tags.items() if k.startswith("attn")) / total, 4),
+                                          gemm=round(sum(t["ms"] for k, t in tags.items() if k.startswith("gemm")) / total, 4),
+                                          sum_of_kernels_ms=round(total, 4))
+        doc["rows"].append(row)
+        print(f"M={M}: encode {row['encode_video']['median_ms']:.2f} ms, score_captions shared {cap:.2f} / per-context "
+              f"{row['score_captions[per-context]']['median_ms']:.2f} ms, forward {row['forward']['median_ms']:.2f} ms", file=sys.stderr, flush=True)
+        del ctx
+
+    if args.matrix:
+        V, M = (int(x) for x in args.matrix.split("x"))
+        tok = CharTokenizer()
+        videos = [synth.synth_pixel_values(7, v, args.frames, args.size).to(dev) for v in range(V)]
+        captions = ["".join(chr(97 + (i * 7 + j) % 26) for j in range(24 + (i * 37) % 73)) for i in range(M)]
+        run = lambda: harness.score_caption_matrix(model, cfg, tok, videos, captions, {}, max_rows=64)  # noqa: E731
+        run()
+        doc["matrix"] = dict(V=V, M=M, **timed(run, max(2, args.reps // 2)),
+                             note="host tokenisation of the V x M prompts included; V encode_video calls + ceil(V M / 64) score_captions calls")
+        # the same call's parts on their own: the V encodes, and ONE score_captions call of V * M rows over V contexts (which
+        # gathers the contexts' rows into one packed buffer per layer) in both attention modes
+        from mj_video_amd.chat_input import prepare_chat_input, video_prefix
+        rows = [[prepare_chat_input(cfg, tok, pv, video_prefix(pv.shape[0]) + c, {}, device="cpu")[0] for c in captions] for pv in videos]
+        ids, mask = harness.pad_right([r for per in rows for r in per], model.config.pad_token_id)
+        ids, mask = ids.to(dev), mask.to(dev)
+        index = torch.tensor([v for v in range(V) for _ in range(M)])
+        ctxs = [model.encode_video(pv, rows[v][0]) for v, pv in enumerate(videos)]
+        doc["matrix"]["encode_video_x_V"] = timed(lambda: [model.encode_video(pv, rows[v][0]) for v, pv in enumerate(videos)], max(2, args.reps // 2))
+        for mode in ("shared", "per-context"):
+            model.caption_attention = mode
+            model.score_captions(ctxs, ids, mask, context_index=index)
+            doc["matrix"][f"score_captions[{mode}]"] = timed(lambda: model.score_captions(ctxs, ids, mask, context_index=index), args.reps)
+        model.caption_attention = "shared"
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
