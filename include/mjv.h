@@ -273,7 +273,9 @@ int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream);
  * modeling_intern_vit.py:291,293; modeling_internvl_chat.py:136).
  * gather_grid > 0 selects the pixel-shuffle gather of modeling_internvl_chat.py:228-242,255-260:
  * output row (tile, a2, b2) is the concatenation of the 4 source rows
- * (2a2,2b2) (2a2,2b2+1) (2a2+1,2b2) (2a2+1,2b2+1) of a [tile][1 + grid*grid][dim/4] buffer (CLS skipped). */
+ * (2a2,2b2) (2a2,2b2+1) (2a2+1,2b2) (2a2+1,2b2+1) of a [tile][1 + grid*grid][dim/4] buffer (CLS skipped).
+ * All the norms below move 16-byte pieces of a row: dim % 8 == 0, dim <= 4096, ldx / ldy % 8 == 0 and x, y, gamma / beta / w
+ * 16-byte aligned (MJV_E_ARG otherwise, before anything is launched). */
 int mjv_layernorm_bf16(const mjv_bf16* x, int64_t ldx, mjv_bf16* y, int64_t ldy, const mjv_bf16* gamma,
                        const mjv_bf16* beta, int32_t rows, int32_t dim, float eps, int32_t gather_grid,
                        void* stream);

@@ -308,6 +308,8 @@ extern "C" int mjv_layernorm_bf16(const mjv_bf16* x, int64_t ldx, mjv_bf16* y, i
   MJV_REQUIRE(x && y && gamma && beta, "layernorm: null pointer");
   MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "layernorm: dim %d unsupported", dim);
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "layernorm: ld alignment");
+  MJV_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0,
+              "layernorm: alignment (16-byte pieces of a row: x, y, gamma, beta must be 16-byte aligned)");
   if (gather_grid > 0) MJV_REQUIRE(gather_grid % 2 == 0 && dim % 32 == 0, "layernorm: gather needs an even grid");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps(gather_grid > 0 ? "layernorm_pixshuf" : "layernorm", s, 0, 4.0 * rows * (double)dim);
@@ -326,6 +328,8 @@ extern "C" int mjv_rmsnorm_bf16(const mjv_bf16* x, int64_t ldx, mjv_bf16* y, int
   MJV_REQUIRE(x && y && w, "rmsnorm: null pointer");
   MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "rmsnorm: dim %d unsupported", dim);
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "rmsnorm: ld alignment");
+  MJV_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) % 16 == 0,
+              "rmsnorm: alignment (16-byte pieces of a row: x, y, w must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("rmsnorm", s, 0, 4.0 * rows * (double)dim);
   const dim3 grid((rows + WAVES - 1) / WAVES);
@@ -342,7 +346,7 @@ extern "C" int mjv_row_stats_bf16(const mjv_bf16* x, int64_t ldx, float* rstd, f
                                   void* stream) {
   MJV_REQUIRE(x && rstd, "row_stats: null pointer");
   MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "row_stats: dim %d unsupported", dim);
-  MJV_REQUIRE(ldx % 8 == 0, "row_stats: ld alignment");
+  MJV_REQUIRE(ldx % 8 == 0 && (uintptr_t)x % 16 == 0, "row_stats: alignment (16-byte pieces of a row: ldx % 8, x 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps(mean_rstd ? "row_stats_ln" : "row_stats_rms", s, 0, 2.0 * rows * (double)dim);
   const dim3 grid((rows + WAVES - 1) / WAVES);
@@ -363,6 +367,8 @@ extern "C" int mjv_layernorm_mxfp8(const mjv_bf16* x, int64_t ldx, uint8_t* y, i
   MJV_REQUIRE(x && y && y_scales && gamma && beta, "layernorm_mxfp8: null pointer");
   MJV_REQUIRE(rows > 0 && dim > 0 && dim % 128 == 0 && dim <= 512 * MAX_IT, "layernorm_mxfp8: dim %d unsupported", dim);
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (uintptr_t)y % 8 == 0, "layernorm_mxfp8: alignment");
+  MJV_REQUIRE(((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0,
+              "layernorm_mxfp8: alignment (x, gamma, beta must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("layernorm_mxfp8", s, 0, 3.03 * rows * (double)dim);
   const dim3 grid((rows + WAVES - 1) / WAVES);
@@ -381,6 +387,7 @@ extern "C" int mjv_rmsnorm_mxfp8(const mjv_bf16* x, int64_t ldx, uint8_t* y, int
   MJV_REQUIRE(x && y && y_scales && w, "rmsnorm_mxfp8: null pointer");
   MJV_REQUIRE(rows > 0 && dim > 0 && dim % 128 == 0 && dim <= 512 * MAX_IT, "rmsnorm_mxfp8: dim %d unsupported", dim);
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (uintptr_t)y % 8 == 0, "rmsnorm_mxfp8: alignment");
+  MJV_REQUIRE(((uintptr_t)x | (uintptr_t)w) % 16 == 0, "rmsnorm_mxfp8: alignment (x, w must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("rmsnorm_mxfp8", s, 0, 3.03 * rows * (double)dim);
   const dim3 grid((rows + WAVES - 1) / WAVES);

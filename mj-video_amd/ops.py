@@ -408,14 +408,16 @@ def row_stats(x: torch.Tensor, rstd: torch.Tensor, mean_rstd: Optional[torch.Ten
                                                 eps, _stream(x)), "mjv_row_stats_bf16")
 
 
-def rope_split(qkv: torch.Tensor, q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+def rope_split(qkv: torch.Tensor, q: Optional[torch.Tensor], k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                positions: torch.Tensor, kv_heads: int, group: int) -> None:
+    """``group`` 0 (include/mjv.h): the rows are [k | v] pairs without q heads, ``q`` is None."""
     _chk_bf16(qkv, q, k, cos, sin)
+    assert (q is None) == (group == 0), "rope_split: q is None exactly when there are no q heads (group 0)"
     assert positions.dtype == torch.int32 and positions.is_cuda
     assert cos.shape[1] == 128 and cos.is_contiguous() and sin.is_contiguous()
     lib = load_library()
     with torch.cuda.device(qkv.device):
-        check(lib.mjv_rope_split_bf16(qkv.data_ptr(), _row_stride(qkv), q.data_ptr(), _row_stride(q), k.data_ptr(),
+        check(lib.mjv_rope_split_bf16(qkv.data_ptr(), _row_stride(qkv), _p(q), (_row_stride(q) if q is not None else 0), k.data_ptr(),
                                       _row_stride(k), cos.data_ptr(), sin.data_ptr(), positions.data_ptr(),
                                       qkv.shape[0], kv_heads, group, _stream(qkv)), "mjv_rope_split_bf16")
 
