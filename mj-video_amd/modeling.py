@@ -18,8 +18,9 @@ from __future__ import annotations
 
 import math
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass, fields
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -109,6 +110,28 @@ class VideoContext:
 
     def tensors(self):
         return self.k + self.v + [self.img_tail]
+
+
+class _Tail(NamedTuple):
+    """``trim_last_layer``: the rows from each sample's first selected one on - all the last decoder layer needs queries for"""
+    rows: torch.Tensor              # their indices among the packed rows
+    pos: torch.Tensor               # their positions
+    cu: Optional[torch.Tensor]      # cumulative tail lengths (device; None where the attention strategy keeps its own)
+    max_len: int                    # longest tail
+    sel: torch.Tensor               # the selected rows' indices among the tail rows
+
+
+class _Snapshot(NamedTuple):
+    """rows [0, P) of every layer's keys / values, kept as the tower computes them (``_build_prefix``, ``encode_video``): the
+    values as the layer's whole wqkv rows, or with ``compact_values`` as the value heads alone ([P, kv heads * 128])"""
+    P: int
+    k: List[torch.Tensor]
+    v: List[torch.Tensor]
+    compact_values: bool = False
+
+
+def _up(a: np.ndarray, dev) -> torch.Tensor:
+    return torch.from_numpy(a).to(dev, non_blocking=True)
 
 
 # ------------------------------------------------------------------------------- parameter holders
@@ -1068,6 +1091,22 @@ class InternVLChatRewardModeling(nn.Module):
             ops.gemm(h, layer.mlp.fc1.weight, f, EPI_BIAS_GELU, bias=layer.mlp.fc1.bias)
         ops.gemm(f, layer.mlp.fc2.weight, x, EPI_SCALE_RES, bias=layer.mlp.fc2.bias, scale=layer.ls2, res=x)
 
+    @contextmanager
+    def _gemm_scratch(self, dev, tag: Optional[str] = None):
+        """The model's device as the current one, and this model's split-K scratch as the default of the GEMMs launched inside
+        (private to this model instance and to the stream the work runs on; ops keeps it per THREAD: another thread scoring
+        with another model instance has its own) - taken back on the way out, not left behind for other gemm callers.
+        ``tag``: the scratch-buffer namespace (``_buf``) of what runs inside."""
+        try:
+            with torch.cuda.device(dev):
+                if tag is not None:
+                    self._ws_tag = tag
+                ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
+                                       if self.use_gemm_workspace else None)
+                yield
+        finally:
+            ops.set_gemm_workspace(None)
+
     @torch.no_grad()
     def run_vit_layer(self, li: int, x: torch.Tensor) -> torch.Tensor:
         """Test entry (not part of the reference's API): encoder layer ``li`` of the vision tower on given hidden states
@@ -1076,18 +1115,13 @@ class InternVLChatRewardModeling(nn.Module):
         vc = self.config.vision_config
         tiles, T, dim = x.shape
         self._prepare(dev)
-        with torch.cuda.device(dev):
-            ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
-                                   if self.use_gemm_workspace else None)
-            try:
-                xs = x.to(dev, BF16).reshape(tiles * T, dim).clone()
-                h = torch.empty_like(xs)
-                qkv = torch.empty(tiles * T, 3 * dim, dtype=BF16, device=dev)
-                f = torch.empty(tiles * T, vc.intermediate_size, dtype=BF16, device=dev)
-                cu = torch.arange(0, (tiles + 1) * T, T, dtype=torch.int32, device=dev)
-                self._vit_layer(self.model.vision_model.encoder.layers[li], xs, h, qkv, f, cu, T, li)
-            finally:
-                ops.set_gemm_workspace(None)
+        with self._gemm_scratch(dev):
+            xs = x.to(dev, BF16).reshape(tiles * T, dim).clone()
+            h = torch.empty_like(xs)
+            qkv = torch.empty(tiles * T, 3 * dim, dtype=BF16, device=dev)
+            f = torch.empty(tiles * T, vc.intermediate_size, dtype=BF16, device=dev)
+            cu = torch.arange(0, (tiles + 1) * T, T, dtype=torch.int32, device=dev)
+            self._vit_layer(self.model.vision_model.encoder.layers[li], xs, h, qkv, f, cu, T, li)
         return xs.view(tiles, T, dim)
 
     @torch.no_grad()
@@ -1098,174 +1132,242 @@ class InternVLChatRewardModeling(nn.Module):
         dev = self.model.device
         d = self._prepare(dev)
         B, N, hd = x.shape
-        with torch.cuda.device(dev):
-            ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
-                                   if self.use_gemm_workspace else None)
-            try:
-                xs = x.to(dev, BF16).reshape(B * N, hd).clone()
-                cu = torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=dev)
-                pos = torch.arange(N, dtype=torch.int32, device=dev).repeat(B)
-                self._language_tower(d, xs, cu, pos, N, None, padded_len=N, only_layer=li)
-            finally:
-                ops.set_gemm_workspace(None)
+        with self._gemm_scratch(dev):
+            xs = x.to(dev, BF16).reshape(B * N, hd).clone()
+            cu = torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=dev)
+            pos = torch.arange(N, dtype=torch.int32, device=dev).repeat(B)
+            self._language_tower(d, xs, cu, pos, N, None, padded_len=N, only_layer=li)
         return xs.view(B, N, hd)
+
+    def _llm_geom(self):
+        """(heads, kv heads, heads per kv head, head_dim, softmax scale, score_round_mode) of the language tower's attention"""
+        lc = self.config.llm_config
+        H, KV = lc.num_attention_heads, lc.num_key_value_heads
+        hd = lc.hidden_size // H
+        # InternLM2: q k^T / sqrt(d) with d = 128: an exact power of two.  Phi-3: q k^T * d^-0.5 with the scaling rounded to fp32
+        # as torch rounds a Python scalar for a bf16 tensor op (modeling_phi3.py: eager_attention_forward)
+        scale = float(np.float32(hd ** -0.5)) if self._phi3 else 1.0 / math.sqrt(hd)
+        return H, KV, H // KV, hd, scale, 2 if self.attention_scores == "flash" else 1
+
+    # The tower takes its attention as a strategy ``attend(li, q, k, v, v_head_stride, out, tail)``: layer ``li``'s queries ``q``
+    # over [what the strategy holds for that layer | the live keys ``k`` / values ``v``] into ``out``; ``tail`` (a ``_Tail``, or
+    # None): ``q`` holds the tail rows only (the trimmed last layer, whose live values lie in a buffer of their own layout).
+    def _attend_live(self, cu: torch.Tensor, max_len: int, prefix):
+        """Strategy of ``forward`` / ``_build_prefix`` / ``encode_video``: the live keys behind the cached ``prefix`` rows (the
+        ``_prefix`` dict, or None).  InternLM2 keeps ``k`` / ``v`` / ``v_last`` rows per layer; Phi-3 keeps the layer's whole
+        [q | k | v] projection rows as ``k`` and the last layer's [k | v] rows as ``kv_last``: column ranges of one tensor."""
+        H, KV, G, hd, scale, mode = self._llm_geom()
+        phi3 = self._phi3
+
+        def attend(li, q, k, v, v_head_stride, out, tail):
+            pk = pv = None
+            if prefix is not None and phi3:
+                rows, c = (prefix["kv_last"], 0) if tail else (prefix["k"][li], H * hd)
+                pk, pv = rows[:, c:c + KV * hd], rows[:, c + KV * hd:]
+            elif prefix is not None:
+                pk, pv = prefix["k"][li], (prefix["v_last"][:, hd:] if tail else prefix["v"][li][:, (G + 1) * hd:])
+            ops.attention(q, k, v, out, cu, max_len, H, G, hd, True, scale, mode, v_head_stride=v_head_stride,
+                          cu_seqlens_q=tail.cu if tail else None, max_seqlen_q=tail.max_len if tail else 0,
+                          prefix_k=pk, prefix_v=pv)
+
+        return attend
+
+    def _attend_contexts_shared(self, ctxs, info, trim: bool, dev):
+        """Strategy of ``score_captions`` (``caption_attention`` "shared"): one mjv_attention_ctx_bf16 launch per layer for every
+        context of the batch"""
+        H, KV, G, hd, scale, mode = self._llm_geom()
+        cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
+        plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev)
+        plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"]) if trim else None
+        ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
+                       dtype=torch.uint8).view(-1)
+        P_all = int(cu_ctx[-1])
+
+        def attend(li, q, k, v, v_head_stride, out, tail):
+            if len(ctxs) == 1:
+                ck, cv = ctxs[0].k[li], ctxs[0].v[li]
+            else:   # the kernel takes the contexts' rows as ONE packed buffer: gathered per layer
+                ck, cv = self._buf("cap_ctx_k", P_all, KV * hd, dev), self._buf("cap_ctx_v", P_all, KV * hd, dev)
+                torch.cat([c.k[li] for c in ctxs], out=ck)
+                torch.cat([c.v[li] for c in ctxs], out=cv)
+            ops.attention_ctx(q, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=v_head_stride)
+
+        return attend
+
+    def _attend_contexts_each(self, ctxs, info, n: int, dev):
+        """Strategy of ``score_captions`` (``caption_attention`` "per-context"), the A/B partner: the existing kernel, one launch
+        per context; its prefix rows share the live rows' layout: compact values"""
+        H, KV, G, hd, scale, mode = self._llm_geom()
+        lens, lens_t = np.diff(info["cu"]), np.diff(info["cu_tail"])
+        cu_d = _up(info["cu"], dev)
+        # sequences [lo, hi) of every context that has any (packed context by context)
+        ranges = [(c, int(np.searchsorted(info["index"], c, "left")), int(np.searchsorted(info["index"], c, "right")))
+                  for c in range(len(ctxs))]
+        ranges = [r for r in ranges if r[2] > r[1]]
+        vc = self._buf("cap_v", n, KV * hd, dev)
+
+        def attend(li, q, k, v, v_head_stride, out, tail):
+            vc.view(n, KV, hd).copy_(torch.as_strided(v, (n, KV, hd), (v.stride(0), v_head_stride, 1)))
+            for c, lo, hi in ranges:
+                ops.attention(q, k, vc, out, cu_d[lo:hi + 1], int(lens[lo:hi].max()), H, G, hd, True, scale, mode,
+                              cu_seqlens_q=tail.cu[lo:hi + 1] if tail else None, max_seqlen_q=int(lens_t[lo:hi].max()) if tail else 0,
+                              prefix_k=ctxs[c].k[li], prefix_v=ctxs[c].v[li])
+
+        return attend
 
     def _language_tower(self, d, x: torch.Tensor, cu: torch.Tensor, positions: torch.Tensor, max_len: int,
                         sel_rows: Optional[torch.Tensor] = None, padded_len: Optional[int] = None,
-                        only_layer: Optional[int] = None, tail=None, prefix=None, snapshot=None):
+                        only_layer: Optional[int] = None, tail: Optional[_Tail] = None, prefix=None,
+                        snapshot: Optional[_Snapshot] = None, attend=None):
         """24 decoder layers in place on the packed rows ``x``.  With ``sel_rows`` (the 2 rows per sample the heads
         read) the LAST layer runs wo / FFN only on those rows - every other row of its output is never used
         (moe_reward.py:211,229,243) - and the [len(sel_rows), hidden] result is returned instead of ``x``.
-        ``tail`` (with ``sel_rows``; ``trim_last_layer``) = (tail_rows, tail_pos, cu_tail, max_tail, sel_in_tail): the last
-        layer computes queries only for those rows.  ``prefix`` = the cached keys / values of the prompt prefix the packed rows
-        leave out (``prefix_cache``); ``snapshot`` (the prefix-only pass of ``_build_prefix``, the context pass of ``encode_video``) =
-        (P, store): keep rows [0, P) of every layer's K / V in ``store["k"]`` / ``store["v"]`` - the values as the layer's whole
-        wqkv rows, or, with ``store["compact_values"]`` set, as the value heads alone ([P, kv heads * 128])."""
+        ``tail`` (with ``sel_rows``; ``trim_last_layer``): the last layer computes queries only for those rows.  ``attend``: the
+        attention strategy (see ``_attend_live``, the default: the live keys behind ``prefix`` = the cached keys / values of the
+        prompt prefix the packed rows leave out, ``prefix_cache``).  ``snapshot`` (the prefix-only pass of ``_build_prefix``, the
+        context pass of ``encode_video``): keep rows [0, P) of every layer's K / V."""
         dev = x.device
         lc = self.config.llm_config
         lm = self.model.language_model.model
-        H, KV = lc.num_attention_heads, lc.num_key_value_heads
-        G = H // KV
-        hd = lc.hidden_size // H
+        H, KV, G, hd, _, _ = self._llm_geom()
         n, hdim = x.shape
-        ff = lc.intermediate_size
         phi3 = self._phi3
-        if phi3:
-            cos, sin = self._rope_tables_phi3(max_len if padded_len is None else padded_len, dev)
-        else:
-            cos, sin = self._rope_tables(max_len if padded_len is None else padded_len, dev)
+        rope = (self._rope_tables_phi3 if phi3 else self._rope_tables)(max_len if padded_len is None else padded_len, dev)
+        if attend is None:
+            attend = self._attend_live(cu, max_len, prefix)
         hn = self._buf("llm_hn", n, hdim, dev)
         qkv = self._buf("llm_qkv", n, (H + 2 * KV) * hd, dev)
-        if not phi3:
-            q = self._buf("llm_q", n, H * hd, dev)
-            k = self._buf("llm_k", n, KV * hd, dev)
-        act = self._buf("llm_act", n, ff, dev)
-        # InternLM2: q k^T / sqrt(d) with d = 128: an exact power of two.  Phi-3: q k^T * d^-0.5 with the scaling rounded to fp32
-        # as torch rounds a Python scalar for a bf16 tensor op (modeling_phi3.py: eager_attention_forward)
-        scale = float(np.float32(hd ** -0.5)) if phi3 else 1.0 / math.sqrt(hd)
-        v_view = qkv[:, (H + KV) * hd:] if phi3 else qkv[:, (G + 1) * hd:]
+        if phi3:   # [q heads | k heads | v heads]: attention reads the three column ranges where they lie
+            q, k, v, vhs = qkv[:, :H * hd], qkv[:, H * hd:(H + KV) * hd], qkv[:, (H + KV) * hd:], hd
+        else:      # q / k go (rotated) to their own buffers, v stays in its columns of qkv
+            q, k = self._buf("llm_q", n, H * hd, dev), self._buf("llm_k", n, KV * hd, dev)
+            v, vhs = qkv[:, (G + 1) * hd:], (G + 2) * hd
+        act = self._buf("llm_act", n, lc.intermediate_size, dev)
         last = len(lm.layers) - 1
-        mode = 2 if self.attention_scores == "flash" else 1
+        e8 = self._exp8_set()
+        probes = self.debug_probes
         for li, layer in enumerate(lm.layers):
             if only_layer is not None and li != only_layer:   # (run_llm_layer: one layer on given rows)
                 continue
-            lfold = d["llm_fold"][li] if self.norm_fusion else None
-            e8 = self._exp8_set()
-            exp8 = bool(e8)
-            trim_here = li == last and sel_rows is not None and self.debug_probes is None and only_layer is None
-            pk = prefix["k"][li] if prefix is not None else None
-            if trim_here and tail is not None and lfold is None and not exp8:
-                # last layer, queries only where the heads will read (trim_last_layer): k | v projection (+ rotary on k) on every
-                # row, the full wqkv on the tail rows, attention of the tail's queries over all keys
-                tail_rows, tail_pos, cu_tail, max_tail, sel_in_tail = tail
-                nt, ns = tail_rows.numel(), sel_rows.numel()
-                kv = self._buf("llm_kv_last", n, 2 * KV * hd, dev)
-                ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
-                if phi3:
-                    # [k heads | v heads] of every row (the k heads rotated in place), q heads of the tail rows only
-                    ops.gemm(hn, d["wkv_last"], kv, EPI_BIAS)
-                    ops.rope_heads(kv, KV, hd, cos, sin, positions)
-                    hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
-                    q_t = self._buf("llm_q_tail", nt, H * hd, dev)
-                    att_t = self._buf("llm_att_tail", nt, H * hd, dev)
-                    ops.embed_gather(tail_rows, hn, hn_t, -1)
-                    ops.gemm(hn_t, d["wq_last"], q_t, EPI_BIAS)
-                    ops.rope_heads(q_t, H, hd, cos, sin, tail_pos)
-                    pl = prefix["kv_last"] if prefix is not None else None
-                    ops.attention(q_t, kv[:, :KV * hd], kv[:, KV * hd:], att_t, cu, max_len, H, G, hd, True, scale, mode,
-                                  cu_seqlens_q=cu_tail, max_seqlen_q=max_tail,
-                                  prefix_k=(pl[:, :KV * hd] if pl is not None else None), prefix_v=(pl[:, KV * hd:] if pl is not None else None))
-                    att_s = self._buf("llm_att_sel", ns, hdim, dev)
-                    x_s = self._buf("llm_x_sel", ns, hdim, dev)
-                    hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
-                    act_s = self._buf("llm_act_sel", ns, ff, dev)
-                    ops.embed_gather(sel_in_tail, att_t, att_s, -1)
-                    ops.embed_gather(sel_rows, x, x_s, -1)
-                    ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
-                    self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
-                    return x_s
-                ops.gemm(hn, d["wkv_last"], kv, EPI_ROPE_QKV, rope=(cos, sin, positions, None, k, 0))
-                hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
-                qkv_t = self._buf("llm_qkv_tail", nt, (H + 2 * KV) * hd, dev)
-                q_t = self._buf("llm_q_tail", nt, H * hd, dev)
-                k_t = self._buf("llm_k_tail", nt, KV * hd, dev)
-                att_t = self._buf("llm_att_tail", nt, H * hd, dev)
-                ops.embed_gather(tail_rows, hn, hn_t, -1)
-                ops.gemm(hn_t, layer.attention.wqkv.weight, qkv_t, EPI_ROPE_QKV, rope=(cos, sin, tail_pos, q_t, k_t, G))
-                ops.attention(q_t, k, kv[:, hd:], att_t, cu, max_len, H, G, hd, True, scale, mode, v_head_stride=2 * hd,
-                              cu_seqlens_q=cu_tail, max_seqlen_q=max_tail,
-                              prefix_k=pk, prefix_v=(prefix["v_last"][:, hd:] if prefix is not None else None))
-                att_s = self._buf("llm_att_sel", ns, hdim, dev)
-                x_s = self._buf("llm_x_sel", ns, hdim, dev)
-                hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
-                act_s = self._buf("llm_act_sel", ns, ff, dev)
-                ops.embed_gather(sel_in_tail, att_t, att_s, -1)
-                ops.embed_gather(sel_rows, x, x_s, -1)
-                ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
-                self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
-                return x_s
-            if phi3:
-                # qkv_proj -> [q heads | k heads | v heads] (modeling_phi3.py:Phi3Attention.forward); the rotary embedding in place on
-                # the q and k heads (one launch: they are consecutive); attention reads the three column ranges where they lie
-                ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
-                ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_BIAS)
-                ops.rope_heads(qkv, H + KV, hd, cos, sin, positions)
-                if snapshot is not None:   # the prompt prefix's projection rows of this layer (rotated k and v in their columns)
-                    snapshot[1]["k"].append(qkv[:snapshot[0]].clone())
-                ops.attention(qkv[:, :H * hd], qkv[:, H * hd:(H + KV) * hd], v_view, hn, cu, max_len, H, G, hd, True, scale, mode,
-                              prefix_k=(pk[:, H * hd:(H + KV) * hd] if pk is not None else None),
-                              prefix_v=(pk[:, (H + KV) * hd:] if pk is not None else None))
-                if self.debug_probes is not None and li == 0:
-                    self.debug_probes["llm_attn0"] = dict(q=qkv[:, :H * hd].clone(), k=qkv[:, H * hd:(H + KV) * hd].clone(),
-                                                          v=v_view.clone(), out=hn.clone(), kv_heads=KV)
-            # wqkv with the rotary embedding + GQA de-interleave in its epilogue: q / k go (rotated) to their own buffers,
-            # v stays in its columns of qkv (modeling_internlm2.py:359-381)
-            elif lfold is not None:
-                rstd = self._buf("llm_rstd", 1, ops.padded_rows(n), dev, dtype=torch.float32).view(-1)
-                ops.row_stats(x, rstd, None, lc.rms_norm_eps)
-                ops.gemm(x, lfold["wqkv"], qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G), folded_norm=(rstd,))
-            elif "wqkv" in e8:
-                h8a = self._buf8("llm_h8a", n, hdim, dev)
-                ops.rmsnorm_mxfp8(x, layer.attention_norm.weight, h8a, lc.rms_norm_eps)
-                ops.gemm(h8a, d["wqkv_8"][li], qkv, EPI_BIAS)
-                ops.rope_split(qkv, q, k, cos, sin, positions, KV, G)
-            else:
-                ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
-                ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G))
-            if snapshot is not None and not phi3:   # the prompt prefix's keys (rotated) and values of this layer
-                snapshot[1]["k"].append(k[:snapshot[0]].clone())
-                if snapshot[1].get("compact_values"):   # (encode_video) the value heads alone: [P, kv heads * 128]
-                    snapshot[1]["v"].append(qkv[:snapshot[0]].view(snapshot[0], KV, G + 2, hd)[:, :, G + 1]
-                                            .clone(memory_format=torch.contiguous_format).view(snapshot[0], KV * hd))
-                else:
-                    snapshot[1]["v"].append(qkv[:snapshot[0]].clone())
-            if not phi3:
-                ops.attention(q, k, v_view, hn, cu, max_len, H, G, hd, True, scale, mode, v_head_stride=(G + 2) * hd,
-                              prefix_k=pk, prefix_v=(prefix["v"][li][:, (G + 1) * hd:] if prefix is not None else None))
-                if self.debug_probes is not None and li == 0:   # operands / result of the first causal attention (parity tests)
-                    self.debug_probes["llm_attn0"] = dict(q=q.clone(), k=k.clone(), v=v_view.clone(), out=hn.clone(), kv_heads=KV)
+            trim_here = li == last and sel_rows is not None and probes is None and only_layer is None
+            if trim_here and tail is not None and not self.norm_fusion and not e8:
+                return (self._phi3_trimmed_last if phi3 else self._llm_trimmed_last)(d, li, layer, x, hn, rope, positions, sel_rows, tail, attend)
+            self._llm_project(d, li, layer, x, hn, qkv, q, k, rope, positions, e8)
+            if snapshot is not None:
+                self._llm_snapshot(snapshot, qkv, k)
+            attend(li, q, k, v, vhs, hn, None)
+            if probes is not None and li == 0:   # operands / result of the first causal attention (parity tests)
+                probes["llm_attn0"] = dict(q=q.clone(), k=k.clone(), v=v.clone(), out=hn.clone(), kv_heads=KV)
             if trim_here:
-                ns = sel_rows.numel()
-                att_s = self._buf("llm_att_sel", ns, hdim, dev)
-                x_s = self._buf("llm_x_sel", ns, hdim, dev)
-                hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
-                act_s = self._buf("llm_act_sel", ns, ff, dev)
-                ops.embed_gather(sel_rows, hn, att_s, -1)     # row gathers (table = activation rows)
-                ops.embed_gather(sel_rows, x, x_s, -1)
-                if "wo" in e8:
-                    ops.gemm(ops.quantize_mxfp8(att_s), d["wo_8"][li], x_s, EPI_SCALE_RES, res=x_s)
-                else:
-                    ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
-                self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
-                return x_s
+                return self._llm_selected_rows(d, li, layer, x, hn, sel_rows, sel_rows)
             if "wo" in e8:
                 ops.gemm(ops.quantize_mxfp8(hn, out=self._buf8("llm_a8a", n, hdim, dev)), d["wo_8"][li], x, EPI_SCALE_RES, res=x)
             else:
                 ops.gemm(hn, layer.attention.wo.weight, x, EPI_SCALE_RES, res=x)
             self._llm_ffn(d, li, layer, x, hn, act, "all")
-            if self.debug_probes is not None:
-                self.debug_probes[f"llm_layer{li}"] = x.clone()
+            if probes is not None:
+                probes[f"llm_layer{li}"] = x.clone()
         return x
+
+    def _llm_project(self, d, li: int, layer, x, hn, qkv, q, k, rope, positions, e8):
+        """attention_norm + wqkv + rotary embedding of an ordinary layer: the rotated queries / keys land in ``q`` / ``k``, the
+        values in their columns of ``qkv`` (``_language_tower`` holds the views)"""
+        lc = self.config.llm_config
+        H, KV = lc.num_attention_heads, lc.num_key_value_heads
+        G = H // KV
+        cos, sin = rope
+        if self._phi3:
+            # qkv_proj -> [q heads | k heads | v heads] (modeling_phi3.py:Phi3Attention.forward); the rotary embedding in place on
+            # the q and k heads (one launch: they are consecutive)
+            ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
+            ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_BIAS)
+            ops.rope_heads(qkv, H + KV, lc.hidden_size // H, cos, sin, positions)
+        # wqkv with the rotary embedding + GQA de-interleave in its epilogue (modeling_internlm2.py:359-381)
+        elif self.norm_fusion:
+            rstd = self._buf("llm_rstd", 1, ops.padded_rows(x.shape[0]), x.device, dtype=torch.float32).view(-1)
+            ops.row_stats(x, rstd, None, lc.rms_norm_eps)
+            ops.gemm(x, d["llm_fold"][li]["wqkv"], qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G), folded_norm=(rstd,))
+        elif "wqkv" in e8:
+            h8a = self._buf8("llm_h8a", x.shape[0], x.shape[1], x.device)
+            ops.rmsnorm_mxfp8(x, layer.attention_norm.weight, h8a, lc.rms_norm_eps)
+            ops.gemm(h8a, d["wqkv_8"][li], qkv, EPI_BIAS)
+            ops.rope_split(qkv, q, k, cos, sin, positions, KV, G)
+        else:
+            ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
+            ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G))
+
+    def _llm_snapshot(self, snapshot: _Snapshot, qkv, k):
+        """keeps the first ``snapshot.P`` rows' keys (rotated) and values of the layer just projected"""
+        P = snapshot.P
+        if self._phi3:   # the layer's whole projection rows (rotated k and v in their columns)
+            snapshot.k.append(qkv[:P].clone())
+            return
+        snapshot.k.append(k[:P].clone())
+        if snapshot.compact_values:
+            lc = self.config.llm_config
+            KV, G, hd = lc.num_key_value_heads, lc.num_attention_heads // lc.num_key_value_heads, lc.hidden_size // lc.num_attention_heads
+            snapshot.v.append(qkv[:P].view(P, KV, G + 2, hd)[:, :, G + 1].clone(memory_format=torch.contiguous_format).view(P, KV * hd))
+        else:
+            snapshot.v.append(qkv[:P].clone())
+
+    def _llm_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend):
+        """InternLM2's last layer, queries only where the heads will read (trim_last_layer): k | v projection (+ rotary on k) on
+        every row, the full wqkv on the tail rows, attention of the tail's queries over all keys"""
+        dev, lc = x.device, self.config.llm_config
+        H, KV, G, hd, _, _ = self._llm_geom()
+        (n, hdim), nt = x.shape, tail.rows.numel()
+        cos, sin = rope
+        k = self._buf("llm_k", n, KV * hd, dev)
+        kv = self._buf("llm_kv_last", n, 2 * KV * hd, dev)
+        ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
+        ops.gemm(hn, d["wkv_last"], kv, EPI_ROPE_QKV, rope=(cos, sin, positions, None, k, 0))
+        hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
+        qkv_t = self._buf("llm_qkv_tail", nt, (H + 2 * KV) * hd, dev)
+        q_t = self._buf("llm_q_tail", nt, H * hd, dev)
+        k_t = self._buf("llm_k_tail", nt, KV * hd, dev)
+        att_t = self._buf("llm_att_tail", nt, H * hd, dev)
+        ops.embed_gather(tail.rows, hn, hn_t, -1)
+        ops.gemm(hn_t, layer.attention.wqkv.weight, qkv_t, EPI_ROPE_QKV, rope=(cos, sin, tail.pos, q_t, k_t, G))
+        attend(li, q_t, k, kv[:, hd:], 2 * hd, att_t, tail)
+        return self._llm_selected_rows(d, li, layer, x, att_t, tail.sel, sel_rows)
+
+    def _phi3_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend):
+        """Phi-3's last layer under trim_last_layer: [k heads | v heads] of every row (the k heads rotated in place), q heads of
+        the tail rows only"""
+        dev, lc = x.device, self.config.llm_config
+        H, KV, G, hd, _, _ = self._llm_geom()
+        (n, hdim), nt = x.shape, tail.rows.numel()
+        cos, sin = rope
+        kv = self._buf("llm_kv_last", n, 2 * KV * hd, dev)
+        ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
+        ops.gemm(hn, d["wkv_last"], kv, EPI_BIAS)
+        ops.rope_heads(kv, KV, hd, cos, sin, positions)
+        hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
+        q_t = self._buf("llm_q_tail", nt, H * hd, dev)
+        att_t = self._buf("llm_att_tail", nt, H * hd, dev)
+        ops.embed_gather(tail.rows, hn, hn_t, -1)
+        ops.gemm(hn_t, d["wq_last"], q_t, EPI_BIAS)
+        ops.rope_heads(q_t, H, hd, cos, sin, tail.pos)
+        attend(li, q_t, kv[:, :KV * hd], kv[:, KV * hd:], hd, att_t, tail)
+        return self._llm_selected_rows(d, li, layer, x, att_t, tail.sel, sel_rows)
+
+    def _llm_selected_rows(self, d, li: int, layer, x, att, att_index, sel_rows):
+        """The last layer's wo / FFN on the rows the heads read alone: rows ``att_index`` of the attention output ``att`` and rows
+        ``sel_rows`` of ``x`` (row gathers: table = activation rows).  Returns the [len(sel_rows), hidden] result."""
+        dev = x.device
+        ns, hdim = sel_rows.numel(), x.shape[1]
+        att_s = self._buf("llm_att_sel", ns, hdim, dev)
+        x_s = self._buf("llm_x_sel", ns, hdim, dev)
+        hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
+        act_s = self._buf("llm_act_sel", ns, self.config.llm_config.intermediate_size, dev)
+        ops.embed_gather(att_index, att, att_s, -1)
+        ops.embed_gather(sel_rows, x, x_s, -1)
+        if "wo" in self._exp8_set():
+            ops.gemm(ops.quantize_mxfp8(att_s), d["wo_8"][li], x_s, EPI_SCALE_RES, res=x_s)
+        else:
+            ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
+        self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
+        return x_s
 
     def _llm_ffn(self, d, li: int, layer, x, hn, act, tag: str):
         """x += w2(silu(w1 h) * w3 h), h = ffn_norm(x)  (modeling_internlm2.py:261-264,669-679) in place on the rows ``x``;
@@ -1312,51 +1414,61 @@ class InternVLChatRewardModeling(nn.Module):
         ops.embed_gather(ids, self.model.language_model.model.tok_embeddings.weight, x, self.model.img_context_token_id)
         cu = torch.tensor([0, P], dtype=torch.int32, device=dev)
         pos = torch.arange(P, dtype=torch.int32, device=dev)
-        store = dict(k=[], v=[])
-        self._language_tower(d, x, cu, pos, P, None, padded_len=padded_len, snapshot=(P, store))
+        store = _Snapshot(P, [], [])
+        self._language_tower(d, x, cu, pos, P, None, padded_len=padded_len, snapshot=store)
         # the last layer's values once more in the [k | v] column layout of the trimmed last layer (wkv_last: kv head h at
         # columns 256 h + 128 ...), copied from their wqkv columns ((G + 2) 128 h + (G + 1) 128 ...): same sums, same values
         if self._phi3:
-            # Phi-3 layout: store["k"][li] = the prefix rows of the layer's whole [q | k | v] projection (the live views' row stride);
+            # Phi-3 layout: store.k[li] = the prefix rows of the layer's whole [q | k | v] projection (the live views' row stride);
             # the trimmed last layer reads [k | v] rows of their own: the same values, copied out
-            kv_last = store["k"][-1][:, H * hd:].contiguous()
+            kv_last = store.k[-1][:, H * hd:].contiguous()
             v_last = kv_last
             extra = dict(kv_last=kv_last)
         else:
             v_last = torch.zeros(P, 2 * KV * hd, dtype=BF16, device=dev)
-            v_last.view(P, KV, 2, hd)[:, :, 1] = store["v"][-1].view(P, KV, G + 2, hd)[:, :, G + 1]
+            v_last.view(P, KV, 2, hd)[:, :, 1] = store.v[-1].view(P, KV, G + 2, hd)[:, :, G + 1]
             extra = {}
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(dev))   # a later forward on ANOTHER stream waits for the rows to exist
-        self._prefix = dict(settings=settings, ids=prefix_ids.copy(), P=P, k=store["k"], v=store["v"], v_last=v_last, ready=ready,
+        self._prefix = dict(settings=settings, ids=prefix_ids.copy(), P=P, k=store.k, v=store.v, v_last=v_last, ready=ready,
                             stream=torch.cuda.current_stream(dev).cuda_stream, **extra)
 
     # -- forward ---------------------------------------------------------------------------------
-    def _forward_group(self, d, tag: str, pixel_values, host_ids, outs, lo: int, probes_ok: bool):
+    def _cache_settings(self, padded_len: int, dev):
+        """What cached keys / values (the system-prefix cache, a ``VideoContext``) depend on besides their token ids: the weights
+        (as _prepare tracks them), the rotary term, every numerics setting, the device.  The rotary term of InternLM2 is the
+        base a forward of padded width ``padded_len`` WILL rotate with (dynamic NTK may have replaced it; the state itself
+        advances in the tower, after the batch is validated); LongRoPE keeps no state: Phi-3's tables depend on whether the
+        padded width exceeds the original window."""
+        lc = self.config.llm_config
+        rot = (int(padded_len) > lc.original_max_position_embeddings if self._phi3
+               else self._rope_next_state(int(padded_len))["base"])
+        return (self._derived_sig, rot, self.attention_scores, self.ffn_format, bool(self.norm_fusion), self._exp8_set(),
+                bool(self.use_gemm_workspace), str(dev))
+
+    def _wait_for_rows(self, dev, stream: int, ready, tensors):
+        """cached rows built on another stream than the current one: wait for them, and tell the allocator who reads them"""
+        cur = torch.cuda.current_stream(dev)
+        if stream != cur.cuda_stream:
+            cur.wait_event(ready)
+            for t in tensors:
+                t.record_stream(cur)
+
+    def _forward_group(self, d, pixel_values, host_ids, outs, lo: int, probes_ok: bool):
         """Scores the batch on the CURRENT stream of the model's device (outputs go to rows [lo, lo+B) of ``outs``).
         ``host_ids``: function returning the (ids, mask) numpy arrays (``_host_ids_begin``) - called only after the vision
         tower's launches are out."""
         dev = pixel_values.device
-        self._ws_tag = tag
-        # split-K scratch of this forward's GEMMs (private to this model instance and to the stream the forward runs on;
-        # ops keeps it per THREAD: another thread scoring with another model instance has its own)
-        ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
-                               if self.use_gemm_workspace else None)
         vit = self._vision_tower_launch(d, pixel_values)     # (needs no ids: enqueued before the host waits for them)
         input_ids, attention_mask = host_ids()
         trimmed = self.debug_probes is None
         lc = self.config.llm_config
         hdim = lc.hidden_size
-        # what the cached prefix rows depend on besides their ids: the weights (as _prepare tracks them), the rotary base
-        # (dynamic NTK may have replaced it), every numerics setting, and which buffer the last layer's values live in
+        # what the cached prefix rows depend on besides their ids: _cache_settings, and (in front of the device) which buffer the
+        # last layer's values live in
         tail_form = bool(trimmed and self.trim_last_layer and not self.norm_fusion and not self._exp8_set())
-        if self._phi3:   # (LongRoPE keeps no state: the tables depend on whether the padded width exceeds the original window)
-            settings = (self._derived_sig, int(input_ids.shape[1]) > lc.original_max_position_embeddings, self.attention_scores,
-                        self.ffn_format, bool(self.norm_fusion), self._exp8_set(), bool(self.use_gemm_workspace), tail_form, str(dev))
-        else:
-            # (the rotary base this forward WILL rotate with - the state itself advances in the tower, after the batch is validated)
-            settings = (self._derived_sig, self._rope_next_state(int(input_ids.shape[1]))["base"], self.attention_scores, self.ffn_format, bool(self.norm_fusion),
-                        self._exp8_set(), bool(self.use_gemm_workspace), tail_form, str(dev))
+        settings = self._cache_settings(input_ids.shape[1], dev)
+        settings = settings[:-1] + (tail_form, settings[-1])
         use_prefix = bool(self.prefix_cache and trimmed)
         hit = []
 
@@ -1393,20 +1505,13 @@ class InternVLChatRewardModeling(nn.Module):
         prefix = self._prefix if info["skip"] else None
         if prefix is not None and hit[0]:
             self.prefix_cache_hits += 1
-            cur = torch.cuda.current_stream(dev)
-            if prefix["stream"] != cur.cuda_stream:   # built on another stream: wait for the rows, and tell the allocator who reads them
-                cur.wait_event(prefix["ready"])
-                for t in prefix["k"] + prefix["v"] + [prefix["v_last"]]:
-                    t.record_stream(cur)
+            self._wait_for_rows(dev, prefix["stream"], prefix["ready"], prefix["k"] + prefix["v"] + [prefix["v_last"]])
 
-        def up(a):
-            return torch.from_numpy(a).to(dev, non_blocking=True)
-
-        ids, positions, cu = up(info["ids"]), up(info["positions"]), up(info["cu"])
-        img_rows, sel_rows = up(info["img_rows"]), up(info["sel_rows"])
+        ids, positions, cu, img_rows, sel_rows = (_up(info[key], dev) for key in ("ids", "positions", "cu", "img_rows", "sel_rows"))
         tail = None
         if tail_form:
-            tail = (up(info["tail_rows"]), up(info["tail_pos"]), up(info["cu_tail"]), info["max_tail"], up(info["sel_in_tail"]))
+            tail = _Tail(_up(info["tail_rows"], dev), _up(info["tail_pos"], dev), _up(info["cu_tail"], dev), info["max_tail"],
+                         _up(info["sel_in_tail"], dev))
         hidden = self._buf("llm_x", total, hdim, dev)
         ops.embed_gather(ids, self.model.language_model.model.tok_embeddings.weight, hidden, self.model.img_context_token_id)
         self._vision_tower_splice(vit, hidden, img_rows)
@@ -1492,12 +1597,6 @@ class InternVLChatRewardModeling(nn.Module):
         if self.model.img_context_token_id is None:
             raise ValueError("model.model.img_context_token_id is not set (eval_genai_mjvideo.py:115)")
 
-    def _caption_settings(self, padded_len: int, dev):
-        """what a VideoContext's keys / values depend on besides its token ids - the tuple ``_forward_group`` builds for the
-        system-prefix cache, without the last layer's buffer form (a context keeps compact rows of its own)"""
-        return (self._derived_sig, self._rope_next_state(int(padded_len))["base"], self.attention_scores, self.ffn_format,
-                bool(self.norm_fusion), self._exp8_set(), bool(self.use_gemm_workspace), str(dev))
-
     @torch.no_grad()
     def encode_video(self, pixel_values: torch.Tensor, input_ids: torch.Tensor,
                      attention_mask: Optional[torch.Tensor] = None) -> VideoContext:
@@ -1541,38 +1640,33 @@ class InternVLChatRewardModeling(nn.Module):
         n_in = int((cols < P).sum())
         lc = self.config.llm_config
         hdim = lc.hidden_size
-        settings = self._caption_settings(N, dev)
+        settings = self._cache_settings(N, dev)
         pixel_values = pixel_values.to(dev).contiguous()
-        try:
-            with torch.cuda.device(dev):
-                self._ws_tag = "g0"
-                ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
-                                       if self.use_gemm_workspace else None)
-                ph, _ = self._vision_tower_launch(d, pixel_values)
-                x = self._buf("llm_x", P, hdim, dev)
-                def up(a):   # through pinned memory: the host does not wait for what the stream is still running
-                    pin = torch.empty(a.shape, dtype=torch.int32, pin_memory=True)
-                    pin.numpy()[...] = a
-                    return pin.to(dev, non_blocking=True)
+        with self._gemm_scratch(dev, "g0"):
+            ph, _ = self._vision_tower_launch(d, pixel_values)
+            x = self._buf("llm_x", P, hdim, dev)
 
-                ops.embed_gather(up(ids[:P]), self.model.language_model.model.tok_embeddings.weight, x, ctx_id)
-                mlp1 = self.model.mlp1
-                if n_in:
-                    ops.gemm(ph[:n_in], mlp1[3].weight, x, EPI_BIAS, bias=mlp1[3].bias,
-                             out_rows=up(cols[:n_in]))
-                img_tail = torch.empty(n_img - n_in, hdim, dtype=BF16, device=dev)
-                if n_img > n_in:
-                    ops.gemm(ph[n_in:n_img], mlp1[3].weight, img_tail, EPI_BIAS, bias=mlp1[3].bias)
-                cu = up(np.asarray([0, P]))
-                pos = torch.arange(P, dtype=torch.int32, device=dev)
-                store = dict(k=[], v=[], compact_values=True)
-                self._language_tower(d, x, cu, pos, P, None, padded_len=N, snapshot=(P, store))
-                ready = torch.cuda.Event()
-                ready.record(torch.cuda.current_stream(dev))
-                stream = torch.cuda.current_stream(dev).cuda_stream
-        finally:
-            ops.set_gemm_workspace(None)
-        return VideoContext(ids[:P].copy(), P, store["k"], store["v"], img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
+            def up(a):   # through pinned memory: the host does not wait for what the stream is still running
+                pin = torch.empty(a.shape, dtype=torch.int32, pin_memory=True)
+                pin.numpy()[...] = a
+                return pin.to(dev, non_blocking=True)
+
+            ops.embed_gather(up(ids[:P]), self.model.language_model.model.tok_embeddings.weight, x, ctx_id)
+            mlp1 = self.model.mlp1
+            if n_in:
+                ops.gemm(ph[:n_in], mlp1[3].weight, x, EPI_BIAS, bias=mlp1[3].bias,
+                         out_rows=up(cols[:n_in]))
+            img_tail = torch.empty(n_img - n_in, hdim, dtype=BF16, device=dev)
+            if n_img > n_in:
+                ops.gemm(ph[n_in:n_img], mlp1[3].weight, img_tail, EPI_BIAS, bias=mlp1[3].bias)
+            cu = up(np.asarray([0, P]))
+            pos = torch.arange(P, dtype=torch.int32, device=dev)
+            store = _Snapshot(P, [], [], compact_values=True)
+            self._language_tower(d, x, cu, pos, P, None, padded_len=N, snapshot=store)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        return VideoContext(ids[:P].copy(), P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
 
     def _analyse_captions(self, ids: np.ndarray, am: Optional[np.ndarray], ctxs, ci: np.ndarray, group: bool):
         """Validates every caption row against its context (nothing is repaired) and derives the packed own rows: what
@@ -1650,102 +1744,6 @@ class InternVLChatRewardModeling(nn.Module):
                     tail_rows=np.concatenate(tail_rows).astype(np.int32), tail_pos=np.concatenate(tail_pos).astype(np.int32),
                     cu_tail=np.asarray(cu_tail, dtype=np.int32), sel_in_tail=np.concatenate([sel_r, sel_g]))
 
-    def _caption_tower(self, d, x: torch.Tensor, info, ctxs, dev):
-        """The decoder layers on the captions' own rows ``x`` (in place), every row attending to [its context | the own rows
-        before it]; the last layer as ``_language_tower`` runs it for a scorer.  Returns the [2 M, hidden] selected rows."""
-        lc = self.config.llm_config
-        lm = self.model.language_model.model
-        H, KV = lc.num_attention_heads, lc.num_key_value_heads
-        G, hd = H // KV, lc.hidden_size // lc.num_attention_heads
-        n, hdim = x.shape
-        ff = lc.intermediate_size
-
-        def up(a):
-            return torch.from_numpy(a).to(dev, non_blocking=True)
-
-        cos, sin = self._rope_tables(info["N"], dev)
-        positions, sel_rows = up(info["positions"]), up(info["sel_rows"])
-        trim = bool(self.trim_last_layer)
-        shared = self.caption_attention == "shared"
-        cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
-        lens, lens_t = np.diff(info["cu"]), np.diff(info["cu_tail"])
-        if shared:
-            plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev)
-            plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"]) if trim else None
-            ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
-                           dtype=torch.uint8).view(-1)
-        else:
-            cu_d, cu_tail_d = up(info["cu"]), up(info["cu_tail"])
-            # sequences [lo, hi) of every context that has any (packed context by context)
-            ranges = [(c, int(np.searchsorted(info["index"], c, "left")), int(np.searchsorted(info["index"], c, "right")))
-                      for c in range(len(ctxs))]
-            ranges = [r for r in ranges if r[2] > r[1]]
-            vc = self._buf("cap_v", n, KV * hd, dev)
-        hn = self._buf("llm_hn", n, hdim, dev)
-        qkv = self._buf("llm_qkv", n, (H + 2 * KV) * hd, dev)
-        q = self._buf("llm_q", n, H * hd, dev)
-        k = self._buf("llm_k", n, KV * hd, dev)
-        act = self._buf("llm_act", n, ff, dev)
-        scale = 1.0 / math.sqrt(hd)
-        mode = 2 if self.attention_scores == "flash" else 1
-        P_all = int(cu_ctx[-1])
-
-        def attend(li, qq, v, vhs, out, tail: bool):
-            if shared:
-                if len(ctxs) == 1:
-                    ck, cv = ctxs[0].k[li], ctxs[0].v[li]
-                else:   # the kernel takes the contexts' rows as ONE packed buffer: gathered per layer
-                    ck, cv = self._buf("cap_ctx_k", P_all, KV * hd, dev), self._buf("cap_ctx_v", P_all, KV * hd, dev)
-                    torch.cat([c.k[li] for c in ctxs], out=ck)
-                    torch.cat([c.v[li] for c in ctxs], out=cv)
-                ops.attention_ctx(qq, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=vhs)
-                return
-            # A/B partner: the existing kernel, one launch per context; its prefix rows share the live rows' layout: compact values
-            vc.view(n, KV, hd).copy_(torch.as_strided(v, (n, KV, hd), (v.stride(0), vhs, 1)))
-            for c, lo, hi in ranges:
-                ops.attention(qq, k, vc, out, cu_d[lo:hi + 1], int(lens[lo:hi].max()), H, G, hd, True, scale, mode,
-                              cu_seqlens_q=cu_tail_d[lo:hi + 1] if tail else None, max_seqlen_q=int(lens_t[lo:hi].max()) if tail else 0,
-                              prefix_k=ctxs[c].k[li], prefix_v=ctxs[c].v[li])
-
-        def selected(li, layer, att, att_index):
-            ns = sel_rows.numel()
-            att_s = self._buf("llm_att_sel", ns, hdim, dev)
-            x_s = self._buf("llm_x_sel", ns, hdim, dev)
-            hn_s = self._buf("llm_hn_sel", ns, hdim, dev)
-            act_s = self._buf("llm_act_sel", ns, ff, dev)
-            ops.embed_gather(att_index, att, att_s, -1)
-            ops.embed_gather(sel_rows, x, x_s, -1)
-            ops.gemm(att_s, layer.attention.wo.weight, x_s, EPI_SCALE_RES, res=x_s)
-            self._llm_ffn(d, li, layer, x_s, hn_s, act_s, "sel")
-            return x_s
-
-        last = len(lm.layers) - 1
-        for li, layer in enumerate(lm.layers):
-            ops.rmsnorm(x, layer.attention_norm.weight, hn, lc.rms_norm_eps)
-            if li == last and trim:
-                # queries only from the first selected row on (trim_last_layer, as _language_tower): k | v of every own row, the
-                # whole wqkv on the tail rows
-                tail_rows, tail_pos = up(info["tail_rows"]), up(info["tail_pos"])
-                nt = tail_rows.numel()
-                kv = self._buf("llm_kv_last", n, 2 * KV * hd, dev)
-                ops.gemm(hn, d["wkv_last"], kv, EPI_ROPE_QKV, rope=(cos, sin, positions, None, k, 0))
-                hn_t = self._buf("llm_hn_tail", nt, hdim, dev)
-                qkv_t = self._buf("llm_qkv_tail", nt, (H + 2 * KV) * hd, dev)
-                q_t = self._buf("llm_q_tail", nt, H * hd, dev)
-                k_t = self._buf("llm_k_tail", nt, KV * hd, dev)
-                att_t = self._buf("llm_att_tail", nt, H * hd, dev)
-                ops.embed_gather(tail_rows, hn, hn_t, -1)
-                ops.gemm(hn_t, layer.attention.wqkv.weight, qkv_t, EPI_ROPE_QKV, rope=(cos, sin, tail_pos, q_t, k_t, G))
-                attend(li, q_t, kv[:, hd:], 2 * hd, att_t, True)
-                return selected(li, layer, att_t, up(info["sel_in_tail"]))
-            ops.gemm(hn, layer.attention.wqkv.weight, qkv, EPI_ROPE_QKV, rope=(cos, sin, positions, q, k, G))
-            attend(li, q, qkv[:, (G + 1) * hd:], (G + 2) * hd, hn, False)
-            if li == last:
-                return selected(li, layer, hn, sel_rows)
-            ops.gemm(hn, layer.attention.wo.weight, x, EPI_SCALE_RES, res=x)
-            self._llm_ffn(d, li, layer, x, hn, act, "all")
-        raise AssertionError("unreachable")
-
     @torch.no_grad()
     def score_captions(self, contexts, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                        context_index=None) -> CustomOutput:
@@ -1779,7 +1777,7 @@ class InternVLChatRewardModeling(nn.Module):
             bad = np.flatnonzero((ci < 0) | (ci >= len(ctxs)))
             if bad.size:
                 raise ValueError(f"row {int(bad[0])}: context_index {int(ci[bad[0]])} out of range ({len(ctxs)} contexts)")
-        settings = self._caption_settings(N, dev)
+        settings = self._cache_settings(N, dev)
         for c, ctx in enumerate(ctxs):
             if ctx.device != dev:
                 raise ValueError(f"context {c} lives on {ctx.device}, the model on {dev}")
@@ -1790,31 +1788,31 @@ class InternVLChatRewardModeling(nn.Module):
         info = self._analyse_captions(ids, am, ctxs, ci, group=self.caption_attention == "per-context")
         outs = self._alloc_outputs(M, dev)
         lc = self.config.llm_config
-        try:
-            with torch.cuda.device(dev):
-                self._ws_tag = "g0"
-                ops.set_gemm_workspace(self._buf("gemm_ws", 1, ops.gemm_workspace_bytes(), dev, dtype=torch.uint8)
-                                       if self.use_gemm_workspace else None)
-                cur = torch.cuda.current_stream(dev)
-                for ctx in ctxs:   # built on another stream: wait for the rows, and tell the allocator who reads them
-                    if ctx.stream != cur.cuda_stream:
-                        cur.wait_event(ctx.ready)
-                        for t in ctx.tensors():
-                            t.record_stream(cur)
-                hidden = self._buf("llm_x", info["total"], lc.hidden_size, dev)
-                ops.embed_gather(torch.from_numpy(info["ids"]).to(dev, non_blocking=True),
-                                 self.model.language_model.model.tok_embeddings.weight, hidden, self.model.img_context_token_id)
-                if (info["img_src"] >= 0).any():   # the image tokens behind the contexts' boundary: their cached embeddings
-                    table = ctxs[0].img_tail if len(ctxs) == 1 else torch.cat([c.img_tail for c in ctxs])
-                    ops.embed_gather(torch.from_numpy(info["img_src"]).to(dev, non_blocking=True), table, hidden, -1)
-                last_x = self._caption_tower(d, hidden, info, ctxs, dev)
-                h_r, h_g = outs["hidden_state"], outs["prompt_embedding"]
-                norm_w = self.model.language_model.model.norm.weight
-                ops.rmsnorm(last_x[:M], norm_w, h_r, lc.rms_norm_eps)
-                ops.rmsnorm(last_x[M:], norm_w, h_g, lc.rms_norm_eps)
-                self._run_heads(d, h_r, h_g, outs, 0, M, dev)
-        finally:
-            ops.set_gemm_workspace(None)
+        shared, trim = self.caption_attention == "shared", bool(self.trim_last_layer)
+        with self._gemm_scratch(dev, "g0"):
+            for ctx in ctxs:
+                self._wait_for_rows(dev, ctx.stream, ctx.ready, ctx.tensors())
+            hidden = self._buf("llm_x", info["total"], lc.hidden_size, dev)
+            ops.embed_gather(_up(info["ids"], dev), self.model.language_model.model.tok_embeddings.weight, hidden,
+                             self.model.img_context_token_id)
+            if (info["img_src"] >= 0).any():   # the image tokens behind the contexts' boundary: their cached embeddings
+                table = ctxs[0].img_tail if len(ctxs) == 1 else torch.cat([c.img_tail for c in ctxs])
+                ops.embed_gather(_up(info["img_src"], dev), table, hidden, -1)
+            # the decoder layers on the captions' own rows, every row attending to [its context | the own rows before it]; the
+            # last layer as ``forward`` runs it for a scorer
+            attend = (self._attend_contexts_shared(ctxs, info, trim, dev) if shared
+                      else self._attend_contexts_each(ctxs, info, info["total"], dev))
+            tail = None
+            if trim:   # (the shared launch reads the tails' offsets from its plan)
+                tail = _Tail(_up(info["tail_rows"], dev), _up(info["tail_pos"], dev), None if shared else _up(info["cu_tail"], dev),
+                             0, _up(info["sel_in_tail"], dev))
+            last_x = self._language_tower(d, hidden, None, _up(info["positions"], dev), 0, _up(info["sel_rows"], dev),
+                                          padded_len=info["N"], tail=tail, attend=attend)
+            h_r, h_g = outs["hidden_state"], outs["prompt_embedding"]
+            norm_w = self.model.language_model.model.norm.weight
+            ops.rmsnorm(last_x[:M], norm_w, h_r, lc.rms_norm_eps)
+            ops.rmsnorm(last_x[M:], norm_w, h_g, lc.rms_norm_eps)
+            self._run_heads(d, h_r, h_g, outs, 0, M, dev)
         self.last_packed34 = outs.pop("packed34")
         return CustomOutput(**outs)
 
@@ -1867,13 +1865,10 @@ class InternVLChatRewardModeling(nn.Module):
         if self.config.pad_token_id is None and B != 1:   # moe_reward.py:218-219
             raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
         outs = self._alloc_outputs(B, dev)
-        try:
-            # the model's device becomes the current device for the whole forward (allocations, events, the library's
-            # per-device kernel attributes), whatever the caller's current device is: model.cuda(1) works like the reference
-            with torch.cuda.device(dev):
-                host_ids = self._host_ids_begin(input_ids, attention_mask)
-                self._forward_group(d, "g0", pixel_values, host_ids, outs, 0, True)
-        finally:   # the split-K scratch is this thread's default in ops: do not leave it behind for other gemm callers
-            ops.set_gemm_workspace(None)
+        # the model's device becomes the current device for the whole forward (allocations, events, the library's
+        # per-device kernel attributes), whatever the caller's current device is: model.cuda(1) works like the reference
+        with self._gemm_scratch(dev, "g0"):
+            host_ids = self._host_ids_begin(input_ids, attention_mask)
+            self._forward_group(d, pixel_values, host_ids, outs, 0, True)
         self.last_packed34 = outs.pop("packed34")
         return CustomOutput(**outs)
