@@ -225,7 +225,8 @@ int mjv_attention_bf16(const mjv_attn_desc* d, void* stream);
  *   Q / K / V / O : the own rows, addressed as in mjv_attn_desc - cu_seqlens: K / V rows; cu_seqlens_q, optional: the queries are
  *       the LAST cu_seqlens_q[s + 1] - cu_seqlens_q[s] own rows, packed at those rows of Q / O.
  *   ctx_k / ctx_v : every context's rows in one packed buffer each, with leading dimensions and head strides of their own;
- *       a context's length is a positive multiple of 64.
+ *       a context's length is a positive multiple of 64.  Or ctx_k_list / ctx_v_list (end of the struct): one base pointer per
+ *       context, no packed buffer.
  *   cu_seqlens / cu_seqlens_q / context_index / cu_context are HOST arrays, read during the call only: every shape is checked
  *       on the host before anything is launched.  What the kernels read is the PLAN, a device copy of the int32 array
  *       mjv_attention_ctx_plan() derives from exactly these arrays (n_heads, kv_group and head_dim included): the caller builds
@@ -260,6 +261,14 @@ typedef struct mjv_attn_ctx_desc {
   int64_t plan_ints;
   void* workspace;               /* DEVICE, 16-byte aligned, private to this stream while the call is in flight */
   int64_t workspace_bytes;       /* >= mjv_attention_ctx_workspace_bytes(d) */
+  /* Contexts where they lie (both NULL = the packed buffers above; one without the other: MJV_E_ARG).  DEVICE arrays
+   * [n_contexts] of device pointers: context c's rows start at ctx_k_list[c] / ctx_v_list[c] (16-byte aligned, at least
+   * cu_context[c + 1] - cu_context[c] rows), every context with the leading dimensions ld_ctx_k / ld_ctx_v and the head strides
+   * ctx_*_head_stride.  cu_context then only gives the lengths, ctx_k / ctx_v are ignored.  The plan is the same for both
+   * addressing modes (a context tile's entry carries its context number), and so are the cut points, the workspace, the merge
+   * and every bit of the result.  The entry cannot read the arrays: what they hold is the caller's to check. */
+  const mjv_bf16* const* ctx_k_list;
+  const mjv_bf16* const* ctx_v_list;
 } mjv_attn_ctx_desc;
 
 /* Reads the index arrays and sizes of `d` only (no device pointer).  plan_host == NULL: returns the number of int32 the plan

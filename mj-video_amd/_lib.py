@@ -66,7 +66,9 @@ class AttnCtxDesc(C.Structure):
                 ("context_index", C.c_void_p), ("cu_context", C.c_void_p), ("n_seqs", C.c_int32), ("n_contexts", C.c_int32),
                 ("n_heads", C.c_int32), ("kv_group", C.c_int32), ("head_dim", C.c_int32), ("causal", C.c_int32),
                 ("scale", C.c_float), ("score_round_mode", C.c_int32), ("plan", C.c_void_p), ("plan_ints", C.c_int64),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                # per-context base pointers (DEVICE arrays [n_contexts]; both NULL = the packed ctx_k / ctx_v)
+                ("ctx_k_list", C.c_void_p), ("ctx_v_list", C.c_void_p)]
 
 
 class HeadsDesc(C.Structure):

@@ -1335,6 +1335,8 @@ struct CtxArgs {
   long ldq, ldk, ldv, ldo;
   int qhs, khs, vhs, ohs;
   const u16 *Kc, *Vc;
+  const u16* const* Kc_list;   // per-context bases (device array), or nullptr: every context in Kc / Vc at its cu_context row
+  const u16* const* Vc_list;
   long ldkc, ldvc;
   int kchs, vchs;
   const int* plan;
@@ -1350,7 +1352,8 @@ struct CtxArgs {
 //   header : {format tag, n_parts, n_tiles, total_q, G, n_kv, 0, 0} - for whoever reads a plan on the host (the tests do); the
 //            kernels get these counts as arguments and never read the header
 //   part   : {tile, first key, end key, 0}
-//   tile   : {0 context / 1 own, first K / V row, keys (host readers only), first part, parts, stacked rows, 0, 0}
+//   tile   : {0 context / 1 own, first K / V row, keys (host readers only), first part, parts, stacked rows, context number
+//            (context tiles; 0 for own tiles), 0}
 MJV_DEV const int* plan_parts(const CtxArgs& p) { return p.plan + HDR; }
 MJV_DEV const int* plan_tiles(const CtxArgs& p) { return plan_parts(p) + (long)p.n_parts * PART_INTS; }
 MJV_DEV const int* plan_rowq(const CtxArgs& p) { return plan_tiles(p) + (long)p.n_tiles * TILE_INTS; }
@@ -1374,8 +1377,12 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
   const int key_row0 = te[1], n_rows = te[5];
   const int QS = TR / p.G;
 
-  const u16* Kg = own ? p.K + (long)kvh * p.khs + (long)key_row0 * p.ldk : p.Kc + (long)kvh * p.kchs + (long)key_row0 * p.ldkc;
-  const u16* Vg = own ? p.V + (long)kvh * p.vhs + (long)key_row0 * p.ldv : p.Vc + (long)kvh * p.vchs + (long)key_row0 * p.ldvc;
+  // a context tile's rows: the packed buffer from the context's first row on, or (per-context bases) the context's own tensor
+  const bool listed = !own && p.Kc_list != nullptr;
+  const u16* Kcb = listed ? p.Kc_list[te[6]] : p.Kc + (long)key_row0 * p.ldkc;
+  const u16* Vcb = listed ? p.Vc_list[te[6]] : p.Vc + (long)key_row0 * p.ldvc;
+  const u16* Kg = own ? p.K + (long)kvh * p.khs + (long)key_row0 * p.ldk : Kcb + (long)kvh * p.kchs;
+  const u16* Vg = own ? p.V + (long)kvh * p.vhs + (long)key_row0 * p.ldv : Vcb + (long)kvh * p.vchs;
   const long ldk = own ? p.ldk : p.ldkc, ldv = own ? p.ldv : p.ldvc;
 
   // this lane's stacked row
@@ -1661,7 +1668,7 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
     for (long i = 0; i < tiles_c; ++i, ++t) {
       int32_t* te = tiles + t * TILE_INTS;
       te[0] = 0; te[1] = d->cu_context[c]; te[2] = clen; te[3] = (int32_t)pt; te[4] = ctx_split[c];
-      te[5] = (int32_t)(std::min((long)QS, ctx_q[c] - i * QS) * G); te[6] = te[7] = 0;
+      te[5] = (int32_t)(std::min((long)QS, ctx_q[c] - i * QS) * G); te[6] = c; te[7] = 0;
       for (int s = 0; s < ctx_split[c]; ++s, ++pt) {
         int32_t* pe = parts + pt * PART_INTS;
         pe[0] = (int32_t)t; pe[1] = s * ctx_chunk[c]; pe[2] = std::min(clen, (s + 1) * ctx_chunk[c]); pe[3] = 0;
@@ -1722,7 +1729,10 @@ extern "C" int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d)
 }
 
 extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) {
-  MJV_REQUIRE(d && d->Q && d->K && d->V && d->O && d->ctx_k && d->ctx_v, "attention_ctx: null pointer");
+  MJV_REQUIRE(d && d->Q && d->K && d->V && d->O, "attention_ctx: null pointer");
+  MJV_REQUIRE(!d->ctx_k_list == !d->ctx_v_list, "attention_ctx: ctx_k_list and ctx_v_list must both be given, or neither");
+  const bool listed = d->ctx_k_list != nullptr;
+  MJV_REQUIRE(listed || (d->ctx_k && d->ctx_v), "attention_ctx: null pointer (ctx_k / ctx_v, or ctx_k_list / ctx_v_list)");
   if (!d->causal) {
     mjv_set_error("attention_ctx: only causal launches are built (a sequence's own rows follow its context)");
     return MJV_E_UNSUPPORTED;
@@ -1735,8 +1745,10 @@ extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) 
               "attention_ctx: ld alignment (multiples of 8 elements)");
   MJV_REQUIRE(d->q_head_stride % 8 == 0 && d->k_head_stride % 8 == 0 && d->v_head_stride % 8 == 0 && d->o_head_stride % 8 == 0 &&
                   d->ctx_k_head_stride % 8 == 0 && d->ctx_v_head_stride % 8 == 0, "attention_ctx: head stride alignment (multiples of 8 elements)");
-  MJV_REQUIRE(((uintptr_t)d->Q | (uintptr_t)d->K | (uintptr_t)d->V | (uintptr_t)d->O | (uintptr_t)d->ctx_k | (uintptr_t)d->ctx_v) % 16 == 0,
+  MJV_REQUIRE(((uintptr_t)d->Q | (uintptr_t)d->K | (uintptr_t)d->V | (uintptr_t)d->O) % 16 == 0 &&
+                  (listed || ((uintptr_t)d->ctx_k | (uintptr_t)d->ctx_v) % 16 == 0),
               "attention_ctx: misaligned pointer (Q, K, V, O, ctx_k, ctx_v must be 16-byte aligned)");
+  MJV_REQUIRE(!listed || ((uintptr_t)d->ctx_k_list | (uintptr_t)d->ctx_v_list) % 8 == 0, "attention_ctx: misaligned ctx_k_list / ctx_v_list");
   MJV_REQUIRE(d->plan && d->plan_ints >= info.ints, "attention_ctx: missing or short plan (%ld ints given, %ld needed: mjv_attention_ctx_plan)",
               (long)(d->plan ? d->plan_ints : 0), (long)info.ints);
   MJV_REQUIRE(d->workspace && d->workspace_bytes >= info.ws_bytes && (uintptr_t)d->workspace % 16 == 0,
@@ -1746,7 +1758,9 @@ extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) 
   a.Q = d->Q; a.K = d->K; a.V = d->V; a.O = d->O;
   a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv; a.ldo = d->ldo;
   a.qhs = d->q_head_stride; a.khs = d->k_head_stride; a.vhs = d->v_head_stride; a.ohs = d->o_head_stride;
-  a.Kc = d->ctx_k; a.Vc = d->ctx_v; a.ldkc = d->ld_ctx_k; a.ldvc = d->ld_ctx_v; a.kchs = d->ctx_k_head_stride; a.vchs = d->ctx_v_head_stride;
+  a.Kc = listed ? nullptr : d->ctx_k; a.Vc = listed ? nullptr : d->ctx_v;
+  a.Kc_list = (const u16* const*)d->ctx_k_list; a.Vc_list = (const u16* const*)d->ctx_v_list;
+  a.ldkc = d->ld_ctx_k; a.ldvc = d->ld_ctx_v; a.kchs = d->ctx_k_head_stride; a.vchs = d->ctx_v_head_stride;
   a.plan = d->plan;
   a.G = d->kv_group; a.n_heads = d->n_heads; a.n_kv = d->n_heads / d->kv_group;
   a.n_parts = (int)info.n_parts; a.n_tiles = (int)info.n_tiles; a.total_q = (int)info.total_q;

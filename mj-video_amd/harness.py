@@ -158,13 +158,17 @@ def score_video_captions(model, config, tokenizer, pixels: torch.Tensor, caption
 
 @torch.no_grad()
 def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor], captions: Sequence[str], generation_config: dict,
-                         max_rows: int = 64) -> torch.Tensor:
+                         max_rows: int = 64, videos_per_call: int = 1) -> torch.Tensor:
     """V videos x M captions (caption-vs-distractor matrices, perturbed captions, re-caption choice): every video is encoded
     once, the V * M caption rows go through ``model.score_captions`` in as few calls as ``max_rows`` rows per call allow.
-    Returns ``[V, M, 1 + n_aspects + n_objectives]`` fp32."""
+    ``videos_per_call`` > 1: the videos go through ``model.encode_videos`` in blocks of that many (one vision-tower and one
+    context pass per block), a block's rows are scored and its contexts dropped before the next block is encoded - the contexts
+    alive at any time are one block's, whatever V is.  Returns ``[V, M, 1 + n_aspects + n_objectives]`` fp32."""
     _lib.assert_product_library()
     if max_rows < 1:
         raise ValueError("max_rows must be positive")
+    if videos_per_call < 1:
+        raise ValueError("videos_per_call must be positive")
     dev = model.model.device
     pad_id = model.config.pad_token_id
     if pad_id is None:
@@ -172,20 +176,37 @@ def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor
     V, M = len(videos), len(captions)
     if not V or not M:
         raise ValueError("score_caption_matrix needs at least one video and one caption")
-    ids, contexts = [], []
-    for pv in videos:
-        pv = pv.to(torch.bfloat16)
-        rows = [prepare_chat_input(config, tokenizer, pv, video_prefix(pv.shape[0]) + c, generation_config, device="cpu")[0] for c in captions]
-        ids.extend(rows)
-        contexts.append(model.encode_video(pv.to(dev), rows[0]))
+
+    def prompts_of(pv):
+        return [prepare_chat_input(config, tokenizer, pv, video_prefix(pv.shape[0]) + c, generation_config, device="cpu")[0] for c in captions]
+
+    def score_rows(ids, contexts, out):
+        """rows r = video-major over ``contexts``; appends the packed rows of every call to ``out``"""
+        n = len(ids)
+        for lo in range(0, n, max_rows):
+            hi = min(n, lo + max_rows)
+            v0, v1 = lo // M, (hi - 1) // M
+            ids_b, mask = pad_right(ids[lo:hi], pad_id)
+            index = torch.tensor([r // M - v0 for r in range(lo, hi)], dtype=torch.int64)
+            model.score_captions(contexts[v0:v1 + 1], ids_b.to(dev), mask.to(dev), context_index=index)
+            out.append(model.last_packed34)
+
     out = []
-    for lo in range(0, V * M, max_rows):
-        hi = min(V * M, lo + max_rows)
-        v0, v1 = lo // M, (hi - 1) // M
-        ids_b, mask = pad_right(ids[lo:hi], pad_id)
-        index = torch.tensor([r // M - v0 for r in range(lo, hi)], dtype=torch.int64)
-        model.score_captions(contexts[v0:v1 + 1], ids_b.to(dev), mask.to(dev), context_index=index)
-        out.append(model.last_packed34)
+    if videos_per_call == 1:
+        ids, contexts = [], []
+        for pv in videos:
+            pv = pv.to(torch.bfloat16)
+            rows = prompts_of(pv)
+            ids.extend(rows)
+            contexts.append(model.encode_video(pv.to(dev), rows[0]))
+        score_rows(ids, contexts, out)
+    else:
+        for b0 in range(0, V, videos_per_call):
+            block = [pv.to(torch.bfloat16) for pv in videos[b0:b0 + videos_per_call]]
+            rows = [prompts_of(pv) for pv in block]
+            contexts = model.encode_videos([pv.to(dev) for pv in block], [r[0] for r in rows])
+            score_rows([r for per in rows for r in per], contexts, out)
+            del contexts
     return torch.cat(out).view(V, M, -1)
 
 

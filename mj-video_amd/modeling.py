@@ -98,7 +98,10 @@ class VideoContext:
     (8 frames @448^2): 8.65 MB per layer, 207.6 MB per video (``nbytes``); the whole wqkv rows ``_build_prefix`` clones for its 64
     system tokens would be 415 MB at this length.
     Valid for the model state it was built under (``settings``: weights as ``_prepare`` tracks them, rotary base, attention
-    numerics, FFN format, norm fusion, device): ``score_captions`` refuses it under any other and never rebuilds it."""
+    numerics, FFN format, norm fusion, device): ``score_captions`` refuses it under any other and never rebuilds it.
+    A context of ``model.encode_videos`` is a VIEW: ``k[layer]`` / ``v[layer]`` / ``img_tail`` are row ranges of buffers the call's
+    videos share, which stay alive as long as any of its contexts does (``storage_nbytes``: what this context keeps alive;
+    ``nbytes``: its own rows).  ``clone()`` gives a context that owns its rows."""
 
     def __init__(self, ids, P, k, v, img_tail, tail_cols, n_img, settings, ready, stream, device):
         self.ids, self.P, self.k, self.v, self.img_tail, self.tail_cols, self.n_img = ids, P, k, v, img_tail, tail_cols, n_img
@@ -108,8 +111,30 @@ class VideoContext:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.tensors())
 
+    @property
+    def storage_nbytes(self) -> int:
+        """bytes of device memory this context keeps alive: every distinct storage behind its tensors, whole (= ``nbytes`` for a
+        context that owns its rows; for a view of ``encode_videos``, the buffers of all the call's videos)"""
+        return sum({s.data_ptr(): s.nbytes() for s in (t.untyped_storage() for t in self.tensors())}.values())
+
     def tensors(self):
         return self.k + self.v + [self.img_tail]
+
+    def clone(self) -> "VideoContext":
+        """an owning copy (same rows, same settings), made on the current stream of the context's device: dropping the other
+        contexts of an ``encode_videos`` call then frees their rows"""
+        ready, stream = self.ready, self.stream
+        if self.device.type == "cuda":
+            cur = torch.cuda.current_stream(self.device)
+            if stream != cur.cuda_stream:
+                cur.wait_event(ready)
+        k, v, img_tail = [t.clone() for t in self.k], [t.clone() for t in self.v], self.img_tail.clone()
+        if self.device.type == "cuda":
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            stream = cur.cuda_stream
+        return VideoContext(self.ids.copy(), self.P, k, v, img_tail, self.tail_cols.copy(), self.n_img, self.settings, ready, stream,
+                            self.device)
 
 
 class _Tail(NamedTuple):
@@ -132,6 +157,13 @@ class _Snapshot(NamedTuple):
 
 def _up(a: np.ndarray, dev) -> torch.Tensor:
     return torch.from_numpy(a).to(dev, non_blocking=True)
+
+
+def _up_pinned(a: np.ndarray, dev) -> torch.Tensor:
+    """an int32 index array through pinned memory: the host does not wait for what the stream is still running"""
+    pin = torch.empty(a.shape, dtype=torch.int32, pin_memory=True)
+    pin.numpy()[...] = a
+    return pin.to(dev, non_blocking=True)
 
 
 # ------------------------------------------------------------------------------- parameter holders
@@ -551,6 +583,10 @@ class InternVLChatRewardModeling(nn.Module):
         # "per-context" = one launch of the existing kernel per context with prefix_k / prefix_v - its A/B partner and a
         # cross-check (tools/caption_bench.py, tests), not a product mode
         self.caption_attention = "shared"
+        # "shared" with more than one context: "in-place" = the launch reads every context's rows where they lie (one table of
+        # per-layer base pointers per call: mjv_attn_ctx_desc.ctx_k_list / ctx_v_list); "packed" = the contexts' rows gathered
+        # into one buffer per layer and operand first - its A/B partner and cross-check (equal bits), not a product mode
+        self.caption_context_rows = "in-place"
 
     # -- construction helpers -------------------------------------------------------------------
     @classmethod
@@ -1174,23 +1210,34 @@ class InternVLChatRewardModeling(nn.Module):
 
     def _attend_contexts_shared(self, ctxs, info, trim: bool, dev):
         """Strategy of ``score_captions`` (``caption_attention`` "shared"): one mjv_attention_ctx_bf16 launch per layer for every
-        context of the batch"""
+        context of the batch.  More than one context (``caption_context_rows``): "in-place" - ONE [layers, 2, contexts] table of
+        the contexts' first-row addresses, uploaded once per call, every layer's launch handed its row; "packed" - the contexts'
+        rows gathered into one buffer per layer."""
         H, KV, G, hd, scale, mode = self._llm_geom()
         cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
         plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev)
         plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"]) if trim else None
         ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
                        dtype=torch.uint8).view(-1)
-        P_all = int(cu_ctx[-1])
+        P_all, C, L = int(cu_ctx[-1]), len(ctxs), len(ctxs[0].k)
+        in_place = C > 1 and self.caption_context_rows == "in-place"
+        if in_place:
+            table = self._buf("cap_ctx_ptrs", L, 2 * C, dev, dtype=torch.int64)
+            table.copy_(torch.from_numpy(np.stack([ops.ctx_pointer_rows([c.k[li] for c in ctxs], [c.v[li] for c in ctxs])
+                                                   for li in range(L)]).reshape(L, 2 * C)))
 
         def attend(li, q, k, v, v_head_stride, out, tail):
-            if len(ctxs) == 1:
+            ptrs = None
+            if C == 1:
                 ck, cv = ctxs[0].k[li], ctxs[0].v[li]
-            else:   # the kernel takes the contexts' rows as ONE packed buffer: gathered per layer
+            elif in_place:
+                ck, cv, ptrs = [c.k[li] for c in ctxs], [c.v[li] for c in ctxs], table[li].view(2, C)
+            else:   # one packed buffer per operand: gathered per layer
                 ck, cv = self._buf("cap_ctx_k", P_all, KV * hd, dev), self._buf("cap_ctx_v", P_all, KV * hd, dev)
                 torch.cat([c.k[li] for c in ctxs], out=ck)
                 torch.cat([c.v[li] for c in ctxs], out=cv)
-            ops.attention_ctx(q, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=v_head_stride)
+            ops.attention_ctx(q, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=v_head_stride,
+                              ctx_list=ptrs)
 
         return attend
 
@@ -1609,35 +1656,10 @@ class InternVLChatRewardModeling(nn.Module):
         caption.  207.6 MB per video for MJ-VIDEO-2B at P = 2 112 (``VideoContext.nbytes``)."""
         dev = self.model.device
         self._caption_guard(dev)
-        if pixel_values.dim() != 4:
-            raise ValueError(f"wrong pixel_values size: {tuple(pixel_values.shape)}")
-        if pixel_values.dtype != BF16:
-            raise TypeError(f"pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
-        ids = input_ids.detach().to("cpu").numpy()
-        if ids.ndim == 2 and ids.shape[0] == 1:
-            ids = ids[0]
-        if ids.ndim != 1:
-            raise ValueError(f"encode_video takes ONE prompt ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
-        N = int(ids.shape[0])
+        a = self._analyse_video(pixel_values, input_ids, attention_mask)
+        ids, N, P, cols, n_img, n_in = a["ids"], a["N"], a["P"], a["cols"], a["n_img"], a["n_in"]
         d = self._prepare(dev)
         ctx_id = self.model.img_context_token_id
-        cols = np.flatnonzero(ids == ctx_id)
-        tiles = int(pixel_values.shape[0])
-        n_img = tiles * self.model.num_image_token
-        if cols.size != n_img or n_img == 0:
-            raise ValueError(f"{cols.size} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {tiles} tiles x "
-                             f"{self.model.num_image_token} image tokens")
-        P = ((int(cols[-1]) + 1) // 64) * 64
-        if P <= 0:
-            raise ValueError(f"the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
-        if attention_mask is not None:
-            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
-            if am.shape[0] != N or not am[:P].all():
-                raise ValueError(f"attention_mask must cover the prompt and be set on all of its first {P} (context) columns")
-        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
-        if int(ids[:P].min()) < 0 or int(ids[:P].max()) >= vocab:
-            raise IndexError(f"token id out of range [0, {vocab})")
-        n_in = int((cols < P).sum())
         lc = self.config.llm_config
         hdim = lc.hidden_size
         settings = self._cache_settings(N, dev)
@@ -1645,28 +1667,128 @@ class InternVLChatRewardModeling(nn.Module):
         with self._gemm_scratch(dev, "g0"):
             ph, _ = self._vision_tower_launch(d, pixel_values)
             x = self._buf("llm_x", P, hdim, dev)
-
-            def up(a):   # through pinned memory: the host does not wait for what the stream is still running
-                pin = torch.empty(a.shape, dtype=torch.int32, pin_memory=True)
-                pin.numpy()[...] = a
-                return pin.to(dev, non_blocking=True)
-
-            ops.embed_gather(up(ids[:P]), self.model.language_model.model.tok_embeddings.weight, x, ctx_id)
+            ops.embed_gather(_up_pinned(ids, dev), self.model.language_model.model.tok_embeddings.weight, x, ctx_id)
             mlp1 = self.model.mlp1
             if n_in:
                 ops.gemm(ph[:n_in], mlp1[3].weight, x, EPI_BIAS, bias=mlp1[3].bias,
-                         out_rows=up(cols[:n_in]))
+                         out_rows=_up_pinned(cols[:n_in], dev))
             img_tail = torch.empty(n_img - n_in, hdim, dtype=BF16, device=dev)
             if n_img > n_in:
                 ops.gemm(ph[n_in:n_img], mlp1[3].weight, img_tail, EPI_BIAS, bias=mlp1[3].bias)
-            cu = up(np.asarray([0, P]))
+            cu = _up_pinned(np.asarray([0, P]), dev)
             pos = torch.arange(P, dtype=torch.int32, device=dev)
             store = _Snapshot(P, [], [], compact_values=True)
             self._language_tower(d, x, cu, pos, P, None, padded_len=N, snapshot=store)
             ready = torch.cuda.Event()
             ready.record(torch.cuda.current_stream(dev))
             stream = torch.cuda.current_stream(dev).cuda_stream
-        return VideoContext(ids[:P].copy(), P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
+        return VideoContext(ids, P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
+
+    def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = ""):
+        """The checks of ``encode_video`` / ``encode_videos`` on ONE video and its prompt ([N] or [1, N]; nothing is repaired), and
+        what the context pass needs of them: the first P ids, P (the column after the last <IMG_CONTEXT>, cut down to a multiple
+        of 64), the <IMG_CONTEXT> columns and how many lie inside P.  Host code: reads the tensors' shapes / dtypes and the ids.
+        ``who``: what the messages of a many-video call start with."""
+        if pixel_values.dim() != 4:
+            raise ValueError(f"{who}wrong pixel_values size: {tuple(pixel_values.shape)}")
+        if pixel_values.dtype != BF16:
+            raise TypeError(f"{who}pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
+        ids = input_ids.detach().to("cpu").numpy()
+        if ids.ndim == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.ndim != 1:
+            raise ValueError(f"{who}ONE prompt per video ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
+        N = int(ids.shape[0])
+        cols = np.flatnonzero(ids == self.model.img_context_token_id)
+        tiles = int(pixel_values.shape[0])
+        n_img = tiles * self.model.num_image_token
+        if cols.size != n_img or n_img == 0:
+            raise ValueError(f"{who}{cols.size} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {tiles} tiles x "
+                             f"{self.model.num_image_token} image tokens")
+        P = ((int(cols[-1]) + 1) // 64) * 64
+        if P <= 0:
+            raise ValueError(f"{who}the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
+        if attention_mask is not None:
+            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
+            if am.shape[0] != N:
+                raise ValueError(f"{who}attention_mask of {am.shape[0]} columns, the prompt has {N}")
+            if not am[:P].all():
+                raise ValueError(f"{who}masked column {int(np.flatnonzero(~am[:P])[0])} inside the context ({P} tokens): "
+                                 "attention_mask must be set on every context column")
+        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
+        if int(ids[:P].min()) < 0 or int(ids[:P].max()) >= vocab:
+            raise IndexError(f"{who}token id out of range [0, {vocab})")
+        return dict(ids=ids[:P].copy(), N=N, P=P, tiles=tiles, n_img=n_img, n_in=int((cols < P).sum()), cols=cols)
+
+    def _analyse_videos(self, pixel_values, input_ids, attention_mask=None):
+        """``encode_videos``' checks - ``_analyse_video`` video by video, every message naming its video - and the packed layout
+        of the context pass.  Host code, as ``_analyse_captions`` is."""
+        if isinstance(pixel_values, torch.Tensor) or isinstance(input_ids, torch.Tensor):
+            raise ValueError("encode_videos takes SEQUENCES of per-video pixel_values [tiles, 3, S, S] and prompts "
+                             "(encode_video takes one video)")
+        pixel_values, input_ids = list(pixel_values), list(input_ids)
+        V = len(pixel_values)
+        if not V:
+            raise ValueError("encode_videos: empty list of videos")
+        masks = [None] * V if attention_mask is None else list(attention_mask)
+        if len(input_ids) != V or len(masks) != V:
+            raise ValueError(f"encode_videos: {V} videos, {len(input_ids)} prompts" +
+                             ("" if attention_mask is None else f", {len(masks)} attention masks"))
+        vids = []
+        for v, (px, ids_t, am_t) in enumerate(zip(pixel_values, input_ids, masks)):
+            vids.append(self._analyse_video(px, ids_t, am_t, who=f"video {v}: "))
+            if tuple(px.shape[1:]) != tuple(pixel_values[0].shape[1:]):
+                raise ValueError(f"video {v}: tiles of {tuple(px.shape[1:])}, video 0 has {tuple(pixel_values[0].shape[1:])} "
+                                 "(one vision-tower pass takes one tile size)")
+        # the packed context rows (video v at rows cu[v] ...) and, behind them, every video's image tokens past its P
+        cu = np.concatenate([[0], np.cumsum([x["P"] for x in vids])]).astype(np.int32)
+        cu_tail = np.concatenate([[0], np.cumsum([x["n_img"] - x["n_in"] for x in vids])]).astype(np.int32)
+        total = int(cu[-1])
+        img_rows = np.concatenate([np.concatenate([cu[v] + x["cols"][:x["n_in"]], total + cu_tail[v] + np.arange(x["n_img"] - x["n_in"])])
+                                   for v, x in enumerate(vids)]).astype(np.int32)
+        return dict(videos=vids, V=V, cu=cu, cu_tail=cu_tail, total=total, max_len=max(x["P"] for x in vids),
+                    N=max(x["N"] for x in vids), ids=np.concatenate([x["ids"] for x in vids]).astype(np.int32),
+                    positions=np.concatenate([np.arange(x["P"]) for x in vids]).astype(np.int32), img_rows=img_rows)
+
+    @torch.no_grad()
+    def encode_videos(self, pixel_values, input_ids, attention_mask=None) -> List[VideoContext]:
+        """``encode_video`` for V videos in one pass: ``pixel_values`` / ``input_ids`` (/ ``attention_mask``) are sequences of what
+        ``encode_video`` takes per video.  ONE vision-tower pass over all tiles, ONE language-tower pass over the sum of the
+        videos' context rows, packed (every video a sequence of its own: positions from 0, causal within the video).  Every
+        layer's rotated keys and compact values land in one buffer per layer for the whole call; the returned contexts are row
+        ranges of those buffers (``VideoContext.clone()`` for an owning copy).  The rotary width is the longest prompt's, and
+        every context carries the settings of that width.  A video's rows are what ``encode_video`` computes for it alone - bit
+        for bit when no GEMM slices K, up to fp32 re-association otherwise."""
+        dev = self.model.device
+        self._caption_guard(dev)
+        info = self._analyse_videos(pixel_values, input_ids, attention_mask)
+        d = self._prepare(dev)
+        lc = self.config.llm_config
+        hdim, total, n_tail = lc.hidden_size, info["total"], int(info["cu_tail"][-1])
+        settings = self._cache_settings(info["N"], dev)
+        px = torch.cat([p.to(dev) for p in pixel_values]).contiguous()
+        with self._gemm_scratch(dev, "g0"):
+            ph, _ = self._vision_tower_launch(d, px)
+            # rows [0, total): the packed context rows; behind them the projected image tokens past each video's P
+            xt = self._buf("llm_x", total + n_tail, hdim, dev)
+            x = xt[:total]
+            ops.embed_gather(_up_pinned(info["ids"], dev), self.model.language_model.model.tok_embeddings.weight, x,
+                             self.model.img_context_token_id)
+            mlp1 = self.model.mlp1
+            ops.gemm(ph, mlp1[3].weight, xt, EPI_BIAS, bias=mlp1[3].bias, out_rows=_up_pinned(info["img_rows"], dev))
+            tails = xt[total:].clone()
+            store = _Snapshot(total, [], [], compact_values=True)
+            self._language_tower(d, x, _up_pinned(info["cu"], dev), _up_pinned(info["positions"], dev), info["max_len"], None,
+                                 padded_len=info["N"], snapshot=store)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        out = []
+        for v, vid in enumerate(info["videos"]):
+            r0, r1, t0, t1 = int(info["cu"][v]), int(info["cu"][v + 1]), int(info["cu_tail"][v]), int(info["cu_tail"][v + 1])
+            out.append(VideoContext(vid["ids"], vid["P"], [k[r0:r1] for k in store.k], [t[r0:r1] for t in store.v], tails[t0:t1],
+                                    vid["cols"][vid["n_in"]:].copy(), vid["n_img"], settings, ready, stream, dev))
+        return out
 
     def _analyse_captions(self, ids: np.ndarray, am: Optional[np.ndarray], ctxs, ci: np.ndarray, group: bool):
         """Validates every caption row against its context (nothing is repaired) and derives the packed own rows: what
@@ -1763,6 +1885,8 @@ class InternVLChatRewardModeling(nn.Module):
             raise ValueError("score_captions: contexts must be a VideoContext or a non-empty list of them (model.encode_video)")
         if self.caption_attention not in ("shared", "per-context"):
             raise ValueError(f"caption_attention {self.caption_attention!r} not in ('shared', 'per-context')")
+        if self.caption_context_rows not in ("in-place", "packed"):
+            raise ValueError(f"caption_context_rows {self.caption_context_rows!r} not in ('in-place', 'packed')")
         if input_ids.dim() != 2:
             raise ValueError(f"input_ids must be [captions, seq], got {tuple(input_ids.shape)}")
         d = self._prepare(dev)

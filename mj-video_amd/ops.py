@@ -296,18 +296,83 @@ class AttnCtxPlan:
         return d
 
 
-def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, ctx_k: torch.Tensor, ctx_v: torch.Tensor,
+def _check_ctx_rows(ctx_k, ctx_v, plan: "AttnCtxPlan", device, k_head_stride: int, v_head_stride: int):
+    """``attention_ctx`` with per-context tensors: every context's keys / values are read WHERE THEY LIE, so each tensor is held
+    to what the launch assumes of all of them before anything is launched - the device, bf16, at least the context's length in
+    rows, a 16-byte aligned first row, one leading dimension per operand, columns for every kv head at the shared head stride.
+    Host code (tensor attributes only).  Returns (ld_ctx_k, ld_ctx_v)."""
+    n_ctx = plan.cu_ctx.size - 1
+    if len(ctx_k) != n_ctx or len(ctx_v) != n_ctx:
+        raise ValueError(f"attention_ctx: {len(ctx_k)} key / {len(ctx_v)} value tensors for the plan's {n_ctx} contexts")
+    lens = plan.cu_ctx[1:] - plan.cu_ctx[:-1]
+    n_kv = plan.n_heads // plan.kv_group
+    lds = []
+    for what, ts, hs in (("keys", ctx_k, k_head_stride), ("values", ctx_v, v_head_stride)):
+        ld = None
+        for c, t in enumerate(ts):
+            who = f"attention_ctx: context {c} ({what})"
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{who}: not a tensor")
+            if t.device != device:
+                raise ValueError(f"{who} lives on {t.device}, the launch on {device}")
+            if t.dtype != BF16:
+                raise TypeError(f"{who}: expected bfloat16, got {t.dtype}")
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{who}: expected 2-D rows of contiguous elements, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.shape[0] < int(lens[c]):
+                raise ValueError(f"{who}: {t.shape[0]} rows, the context has {int(lens[c])}")
+            if t.shape[1] < (n_kv - 1) * hs + plan.head_dim:
+                raise ValueError(f"{who}: {t.shape[1]} columns do not hold {n_kv} heads of {plan.head_dim} at head stride {hs}")
+            if t.data_ptr() % 16:
+                raise ValueError(f"{who}: its first row is not 16-byte aligned")
+            if ld is None:
+                ld = t.stride(0)
+            elif t.stride(0) != ld:
+                raise ValueError(f"{who}: leading dimension {t.stride(0)}, context 0 has {ld} (one stride for every context)")
+        lds.append(ld)
+    return lds[0], lds[1]
+
+
+def ctx_pointer_rows(ctx_k, ctx_v) -> "np.ndarray":
+    """host int64 [2, contexts]: the first-row addresses of every context's keys (row 0) and values (row 1) - what
+    ``attention_ctx`` takes, uploaded, as ``ctx_list``"""
+    import numpy as np
+    return np.asarray([[t.data_ptr() for t in ctx_k], [t.data_ptr() for t in ctx_v]], dtype=np.int64)
+
+
+def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, ctx_k, ctx_v,
                   plan: AttnCtxPlan, scale: float, score_round_mode: int, workspace: Optional[torch.Tensor],
                   q_head_stride: Optional[int] = None, k_head_stride: Optional[int] = None, v_head_stride: Optional[int] = None,
                   o_head_stride: Optional[int] = None, ctx_k_head_stride: Optional[int] = None,
-                  ctx_v_head_stride: Optional[int] = None, causal: bool = True) -> torch.Tensor:
+                  ctx_v_head_stride: Optional[int] = None, causal: bool = True,
+                  ctx_list: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal attention of every sequence's own rows (q / k / v / out: 2-D views as in ``attention``) over
-    [its context's rows of ``ctx_k`` / ``ctx_v`` | its own rows] (include/mjv.h, mjv_attention_ctx_bf16).  ``plan``: the batch's
+    [its context's rows | its own rows] (include/mjv.h, mjv_attention_ctx_bf16).  ``ctx_k`` / ``ctx_v``: every context's rows in ONE
+    packed tensor each (context c at rows ``plan.cu_ctx[c]`` ...), or both a SEQUENCE of one tensor per context, read where they
+    lie (ctx_k_list / ctx_v_list of the descriptor; every tensor is checked here, before any launch: ``_check_ctx_rows``).
+    ``ctx_list`` (with sequences): a device int64 tensor [2, contexts] holding ``ctx_pointer_rows(ctx_k, ctx_v)`` - a caller with
+    many launches over the same contexts uploads all its rows once; None: uploaded here.  ``plan``: the batch's
     ``AttnCtxPlan``; ``workspace``: a uint8 device tensor of at least ``plan.workspace_bytes`` (the library allocates nothing)."""
-    _chk_bf16(q, k, v, out, ctx_k, ctx_v)
     hd = plan.head_dim
+    kchs = hd if ctx_k_head_stride is None else ctx_k_head_stride
+    vchs = hd if ctx_v_head_stride is None else ctx_v_head_stride
+    listed = [not isinstance(t, torch.Tensor) for t in (ctx_k, ctx_v)]
+    if listed[0] != listed[1]:
+        raise ValueError("attention_ctx: ctx_k and ctx_v must both be one packed tensor, or both a sequence of per-context tensors")
+    listed = listed[0]
+    if listed:
+        ctx_k, ctx_v = list(ctx_k), list(ctx_v)
+        ld_ck, ld_cv = _check_ctx_rows(ctx_k, ctx_v, plan, q.device, kchs, vchs)
+        if ctx_list is not None and (ctx_list.dtype != torch.int64 or ctx_list.device != q.device or not ctx_list.is_contiguous()
+                                     or tuple(ctx_list.shape) != (2, len(ctx_k))):
+            raise ValueError(f"attention_ctx: ctx_list must be a contiguous int64 tensor [2, {len(ctx_k)}] on {q.device}")
+    elif ctx_list is not None:
+        raise ValueError("attention_ctx: ctx_list goes with per-context tensors, not with packed ctx_k / ctx_v")
+    _chk_bf16(q, k, v, out)
+    if not listed:
+        _chk_bf16(ctx_k, ctx_v)
     if q.shape[0] < plan.total_q or out.shape[0] < plan.total_q or k.shape[0] < int(plan.cu[-1]) or v.shape[0] < int(plan.cu[-1]) \
-            or ctx_k.shape[0] < int(plan.cu_ctx[-1]) or ctx_v.shape[0] < int(plan.cu_ctx[-1]):
+            or (not listed and (ctx_k.shape[0] < int(plan.cu_ctx[-1]) or ctx_v.shape[0] < int(plan.cu_ctx[-1]))):
         raise ValueError("attention_ctx: a tensor holds fewer rows than the plan's index arrays address")
     if workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_cuda):
         raise TypeError("attention_ctx: workspace must be a uint8 device tensor")
@@ -318,9 +383,14 @@ def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
     d.k_head_stride = hd if k_head_stride is None else k_head_stride
     d.v_head_stride = hd if v_head_stride is None else v_head_stride
     d.o_head_stride = hd if o_head_stride is None else o_head_stride
-    d.ctx_k, d.ctx_v, d.ld_ctx_k, d.ld_ctx_v = ctx_k.data_ptr(), ctx_v.data_ptr(), _row_stride(ctx_k), _row_stride(ctx_v)
-    d.ctx_k_head_stride = hd if ctx_k_head_stride is None else ctx_k_head_stride
-    d.ctx_v_head_stride = hd if ctx_v_head_stride is None else ctx_v_head_stride
+    if listed:
+        if ctx_list is None:
+            ctx_list = torch.from_numpy(ctx_pointer_rows(ctx_k, ctx_v)).to(q.device)
+        d.ctx_k_list, d.ctx_v_list = ctx_list[0].data_ptr(), ctx_list[1].data_ptr()
+        d.ld_ctx_k, d.ld_ctx_v = ld_ck, ld_cv
+    else:
+        d.ctx_k, d.ctx_v, d.ld_ctx_k, d.ld_ctx_v = ctx_k.data_ptr(), ctx_v.data_ptr(), _row_stride(ctx_k), _row_stride(ctx_v)
+    d.ctx_k_head_stride, d.ctx_v_head_stride = kchs, vchs
     d.causal, d.scale, d.score_round_mode = int(causal), scale, score_round_mode
     d.plan, d.plan_ints = plan.plan.data_ptr(), plan.plan_ints
     if workspace is not None:

@@ -3,11 +3,13 @@
     python tools/caption_bench.py [--m 1,2,4,8,16,64] [--reps 5] [--out FILE.json] [--matrix 8x8] [--size 448] [--frames 8]
 
 MJ-VIDEO-2B dims, random-init weights generated on the device (bench.py's), 8 frames @448^2, captions of 24 - 96 tokens.
-Per M: ms of ``encode_video``; ms of ``score_captions`` with caption_attention "shared" and "per-context" (alternated rep by rep
+(``--m ""``: the matrix part alone.)  Per M: ms of ``encode_video``; ms of ``score_captions`` with caption_attention "shared" and "per-context" (alternated rep by rep
 in this one process); ms of ``forward`` on the M full prompts in batches of at most 8 videos (all the model could do before:
 the baseline); captions/s.  Every shape is warmed first; a timed region is bracketed by device events and ends in a
 synchronise.  Then the library profiler's per-tag table of one caption pass (attention share, small-GEMM share) and V x M
-through ``harness.score_caption_matrix``.  One JSON document on stdout (and in --out).
+through ``harness.score_caption_matrix`` - one video per ``encode_video`` call against all V through ONE ``encode_videos`` call,
+and one ``score_captions`` call over the V contexts with ``caption_context_rows`` "packed" against "in-place" - the arms of
+every pair alternated rep by rep.  One JSON document on stdout (and in --out).
 """
 import argparse
 import json
@@ -95,7 +97,7 @@ def main():
             hi = min(M, lo + 8)
             model.forward(px.repeat(hi - lo, 1, 1, 1), ids[lo:hi], mask[lo:hi])
 
-    for M in [int(x) for x in args.m.split(",")]:
+    for M in [int(x) for x in args.m.split(",") if x]:
         prompts = prompts_of(M)
         ids, mask = synth.pad_batch(prompts)
         ids, mask = ids.to(dev), mask.to(dev)
@@ -139,28 +141,54 @@ def main():
         del ctx
 
     if args.matrix:
+        from mj_video_amd.chat_input import prepare_chat_input, video_prefix
         V, M = (int(x) for x in args.matrix.split("x"))
         tok = CharTokenizer()
         videos = [synth.synth_pixel_values(7, v, args.frames, args.size).to(dev) for v in range(V)]
         captions = ["".join(chr(97 + (i * 7 + j) % 26) for j in range(24 + (i * 37) % 73)) for i in range(M)]
-        run = lambda: harness.score_caption_matrix(model, cfg, tok, videos, captions, {}, max_rows=64)  # noqa: E731
-        run()
-        doc["matrix"] = dict(V=V, M=M, **timed(run, max(2, args.reps // 2)),
-                             note="host tokenisation of the V x M prompts included; V encode_video calls + ceil(V M / 64) score_captions calls")
-        # the same call's parts on their own: the V encodes, and ONE score_captions call of V * M rows over V contexts (which
-        # gathers the contexts' rows into one packed buffer per layer) in both attention modes
-        from mj_video_amd.chat_input import prepare_chat_input, video_prefix
+        reps = max(2, args.reps)
+
+        def alternated(arms):
+            """{name: fn} -> {name: median / min ms}: every arm warmed once, then the arms in turn, ``reps`` rounds"""
+            for fn in arms.values():
+                fn()
+            ms = {name: [] for name in arms}
+            for _ in range(reps):
+                for name, fn in arms.items():
+                    ms[name].append(timed(fn, 1)["median_ms"])
+            return {name: dict(median_ms=statistics.median(v), min_ms=min(v), reps=len(v), all_ms=[round(x, 3) for x in v])
+                    for name, v in ms.items()}
+
+        def matrix(per_call):
+            return lambda: harness.score_caption_matrix(model, cfg, tok, videos, captions, {}, max_rows=64, videos_per_call=per_call)
+
+        doc["matrix"] = dict(V=V, M=M, note="host tokenisation of the V x M prompts included; ceil(V M / 64) score_captions calls",
+                             score_caption_matrix=alternated({"videos_per_call=1": matrix(1), f"videos_per_call={V}": matrix(V)}))
+        # the same call's parts on their own: the V encodes (one call per video / one call for all), and ONE score_captions
+        # call of V * M rows over V contexts: contexts read in place / gathered into one packed buffer per layer / one launch per
+        # context
         rows = [[prepare_chat_input(cfg, tok, pv, video_prefix(pv.shape[0]) + c, {}, device="cpu")[0] for c in captions] for pv in videos]
         ids, mask = harness.pad_right([r for per in rows for r in per], model.config.pad_token_id)
         ids, mask = ids.to(dev), mask.to(dev)
         index = torch.tensor([v for v in range(V) for _ in range(M)])
-        ctxs = [model.encode_video(pv, rows[v][0]) for v, pv in enumerate(videos)]
-        doc["matrix"]["encode_video_x_V"] = timed(lambda: [model.encode_video(pv, rows[v][0]) for v, pv in enumerate(videos)], max(2, args.reps // 2))
-        for mode in ("shared", "per-context"):
-            model.caption_attention = mode
-            model.score_captions(ctxs, ids, mask, context_index=index)
-            doc["matrix"][f"score_captions[{mode}]"] = timed(lambda: model.score_captions(ctxs, ids, mask, context_index=index), args.reps)
-        model.caption_attention = "shared"
+        firsts = [rows[v][0] for v in range(V)]
+        doc["matrix"]["encode"] = alternated({"encode_video_x_V": lambda: [model.encode_video(pv, firsts[v]) for v, pv in enumerate(videos)],
+                                              "encode_videos": lambda: model.encode_videos(videos, firsts)})
+
+        def score(ctxs, rows_mode, attention):
+            def run():
+                model.caption_context_rows, model.caption_attention = rows_mode, attention
+                model.score_captions(ctxs, ids, mask, context_index=index)
+            return run
+
+        owned = [model.encode_video(pv, firsts[v]) for v, pv in enumerate(videos)]
+        views = model.encode_videos(videos, firsts)
+        doc["matrix"]["context_bytes"] = dict(per_video=owned[0].nbytes, view_keeps_alive=views[0].storage_nbytes)
+        doc["matrix"]["score_captions"] = alternated({"shared,packed": score(owned, "packed", "shared"),
+                                                      "shared,in-place": score(owned, "in-place", "shared"),
+                                                      "shared,in-place,views": score(views, "in-place", "shared"),
+                                                      "per-context": score(owned, "in-place", "per-context")})
+        model.caption_context_rows, model.caption_attention = "in-place", "shared"
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:
