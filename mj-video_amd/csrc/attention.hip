@@ -86,11 +86,6 @@ struct Cfg {
 //            modeling_intern_vit.py:229-244, modeling_internlm2.py:437-561; API score_round_mode 2, attn2_kernel only]
 enum { RM_MUL = 0, RM_DIV = 1, RM_POW2 = 2, RM_FLASH = 3 };
 
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-// two fp32 -> packed bf16 pair in one v_cvt_pk_bf16_f32
-MJV_DEV unsigned pack_pair(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
 // round two fp32 values through bf16: two conversions with the value in the high half (mjv_common.h rbf) instead of one
 // packed conversion + shift + mask - 2 vector instructions per pair instead of 3 on the softmax's critical resource
 MJV_DEV f32x2 round_pair(f32x2 v) { return f32x2{rbf(v[0]), rbf(v[1])}; }
@@ -337,7 +332,7 @@ __global__ __launch_bounds__(256, (D == 64) ? 4 : 2) void attn_kernel(AttnArgs p
       for (int t2 = 0; t2 < 2; ++t2) {
         unsigned pw[8];
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) pw[r >> 1] = pack_pair(f32x2{sacc[t2][r], sacc[t2][r + 1]});
+        for (int r = 0; r < 16; r += 2) pw[r >> 1] = pack2(f32x2{sacc[t2][r], sacc[t2][r + 1]});
         pf[t2][0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
         pf[t2][1] = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
       }
@@ -377,7 +372,7 @@ __global__ __launch_bounds__(256, (D == 64) ? 4 : 2) void attn_kernel(AttnArgs p
         const f32x2 e2 = sr * c2 + nmb2;
         const f32x2 pv = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};
         psum2 += pv;
-        pw[r >> 1] = pack_pair(pv);
+        pw[r >> 1] = pack2(pv);
       }
       pf[t2][0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
       pf[t2][1] = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
@@ -866,8 +861,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn2_kernel(AttnArgs p) {
     }
     const f32x2 e2 = sr * c2 + f32x2{nmb, nmb};
     const f32x2 pv = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};
-    pw = pack_pair(pv);
-    psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, pw), __builtin_bit_cast(bf16x2v, 0x3f803f80u), psum, false);
+    pw = pack2(pv);
+    psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pw), __builtin_bit_cast(bf16x2, 0x3f803f80u), psum, false);
   };
   // rare path: raise the offset of sub-block sb to cover unit scores S, rescale its state, recompute the unit's P
   auto redo = [&](const f32x16& S, auto sbc, float& psum, unsigned (&pw)[8]) __attribute__((always_inline)) {
@@ -1443,8 +1438,8 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
     else sr = round_pair(round_pair(a2) * scale2);      // RM_DIV: bf16(bf16(acc) * scale)
     const f32x2 e2 = sr * c2 + f32x2{nmb, nmb};
     const f32x2 pv = {__builtin_amdgcn_exp2f(e2[0]), __builtin_amdgcn_exp2f(e2[1])};
-    pw = pack_pair(pv);
-    psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, pw), __builtin_bit_cast(bf16x2v, 0x3f803f80u), psum, false);
+    pw = pack2(pv);
+    psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pw), __builtin_bit_cast(bf16x2, 0x3f803f80u), psum, false);
   };
   auto redo = [&](const f32x16& S, float& psum, unsigned (&pw)[8]) __attribute__((always_inline)) {
     float mx = S[0];

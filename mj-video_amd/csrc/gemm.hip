@@ -27,30 +27,10 @@
 // and the epilogue moves 8 bytes per lane per access.
 //
 // Epilogues reproduce the reference's bf16 op boundaries (one rounding per torch op).
-#include "mjv_common.h"
-#include "gelu_table.h"
+#include "gemm_common.h"
 #include <atomic>
 
 namespace {
-
-// exact-erf GELU on bf16 as a finite function (tools/gen_gelu_table.py): bit-identical to torch's CPU bf16 GELU
-__device__ const u16 g_gelu_table[MJV_GELU_TABLE_LEN] = MJV_GELU_TABLE_INIT;
-
-// x given as an fp32 value that is exactly representable in bf16; tab = table in LDS or global memory.
-// Branch-free on purpose (selects only): a divergent version costs ~3x more than the table read it guards.
-MJV_DEV float gelu_lut(float xf, const u16* tab) {
-  const unsigned u = __float_as_uint(xf);
-  const unsigned mag = (u >> 16) & 0x7fffu;
-  const unsigned rel = mag - MJV_GELU_LO;                       // wraps to a huge value below the table
-  const unsigned sgn = (unsigned)((int)u >> 31);                // all ones for x < 0
-  const bool in_tab = rel < (unsigned)MJV_GELU_R;
-  const unsigned idx = in_tab ? rel + (sgn & MJV_GELU_NEG_OFF) : 0u;
-  const unsigned t = tab[idx];
-  const unsigned big = gelu_beyond_table(u, mag);               // beyond the table (mjv_common.h)
-  const unsigned small = __float_as_uint(0.5f * xf);            // below the table: x / 2
-  const unsigned other = mag < MJV_GELU_LO ? small : big;
-  return __uint_as_float(in_tab ? (t << 16) : other);
-}
 
 struct GemmArgs {
   const u16* A; long lda;
@@ -78,25 +58,6 @@ struct GemmArgs {
   // norm folded into the consumer (mjv.h "row_scale"): lin = row_scale[m] * acc - row_shift[m] * col_shift[n] + bias
   const float *row_scale, *row_shift, *col_shift, *bias_f32;
 };
-
-// x * rcp(1 + e^-x): v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division; the result is rounded to bf16 next, and
-// e^-x is a 1-2 ulp v_exp_f32 already, so the quotient's last fp32 bit carries no information the reference shares
-MJV_DEV float silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-MJV_DEV unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-
-// 16-byte output store, streaming (nt) on request.  The nt form is inline assembly: written as `if (nt)
-// __builtin_nontemporal_store(...) else plain store`, hipcc (ROCm 7.2) merges the two arms into ONE plain store and the hint is
-// gone (the kernels of rounds 1-3 contained no nt store at all - found in round 4 by reading the ISA).  Counted in vmcnt like
-// any store; nothing ever waits for it.
-MJV_DEV void store16(u16* dst, const u32x4& val, int nt) {
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(val) : "memory");
-  else *(u32x4*)dst = val;
-}
 
 MJV_DEV long out_row_of(const GemmArgs& p, int m) {
   if (p.out_rows) return p.out_rows[m];
@@ -220,24 +181,11 @@ MJV_DEV void store_frags(const GemmArgs& p, const f32x4* acc /* [NI][NJ] */, con
   }
 }
 
-MJV_DEV void tile_of_vblock(const GemmArgs& p, int nwg, int b, int& tm, int& tn);
-MJV_DEV void tile_of_block(const GemmArgs& p, int& tm, int& tn) { tile_of_vblock(p, gridDim.x, blockIdx.x, tm, tn); }
+// XCD-aware tile order (gemm_common.h): b-th of nwg tiles
 MJV_DEV void tile_of_vblock(const GemmArgs& p, const int nwg, const int b, int& tm, int& tn) {
-  // XCD-aware tile order.  Blocks b and b+8 share an XCD (round-robin dispatch), so every XCD gets a contiguous range
-  // of a tile list that is itself ordered in groups of GM m-tiles x all n-tiles, n-major inside a group: the ~32
-  // tiles an XCD runs concurrently then form a GM x (32/GM) patch that shares GM activation panels and 32/GM weight
-  // panels through that XCD's 4 MiB L2 (row-major order shares 1 + 32 panels: the whole weight matrix was re-fetched
-  // over the fabric once per m-tile row - rocprofv3 FETCH_SIZE 4.7 GB per w1|w3 launch for 139 MB of operands).
-  const int GM = p.gm;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
-  const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
-  const int per_group = GM * p.tiles_n;
-  const int grp = t / per_group, in_grp = t - grp * per_group;
-  const int first_m = grp * GM;
-  const int gsz = min(p.tiles_m - first_m, GM);
-  tn = in_grp / gsz;
-  tm = first_m + (in_grp - tn * gsz);
+  xcd_tile_order(p.gm, p.tiles_m, p.tiles_n, nwg, b, tm, tn);
 }
+MJV_DEV void tile_of_block(const GemmArgs& p, int& tm, int& tn) { tile_of_vblock(p, gridDim.x, blockIdx.x, tm, tn); }
 
 // ============================================================================================ 128 x 128
 namespace t128 {
@@ -527,13 +475,13 @@ constexpr int ST_OFF = LDS_BYTES;
 constexpr int LDS_BYTES_FUSE = LDS_BYTES + 4096;
 static_assert(ST_OFF % 16 == 0 && LDS_BYTES_FUSE <= 160 * 1024, "LDS budget (fused norm)");
 
-// GELU kernels (round 4): the table's two sign halves sit 64 KiB apart - x > 0 at LDS byte 0, x < 0 at byte 65536 - so that
+// GELU kernels (round 4): the table's two sign halves sit 64 KiB apart (gemm_common.h GELU_SPLIT_NEG) - so that
 // the gather address is the rounded value's own bit pattern: (fp32 bits >> 15) - 2 LO = 65536 sign + 2 (magnitude - LO), two
 // vector instructions where the contiguous table took five (magnitude, -LO, sign mask, & R, +) and a per-element range
 // compare.  A 16-KiB pipeline slot is given up at each of the two addresses (the eight half-tiles use slots 1-3 and 5-9 of the
 // ten the 160 KiB hold), the folded-norm vectors go behind the first table, and the staged output tile - which no longer has
 // 132 contiguous KiB - is split into rows 0..100 below the second table and rows 101..255 above it.
-constexpr int G_NEG = 65536;
+constexpr int G_NEG = GELU_SPLIT_NEG;
 constexpr int G_ST = 7680;                       // FUSE vectors (4 KiB), behind the 7 680-byte table half
 constexpr int G_A0 = G_ST + 4096, G_AROWS = (G_NEG - G_A0) / EPI_PITCH;     // rows 0 .. G_AROWS - 1
 constexpr int G_B0 = G_NEG + 7680;                                            // rows G_AROWS .. 255
@@ -548,47 +496,7 @@ template <bool GL>
 MJV_DEV int erow_off(int ml) {    // LDS byte offset of row ml of the staged output tile
   return GL ? ml * EPI_PITCH + (ml < G_AROWS ? G_A0 : G_B0 - G_AROWS * EPI_PITCH) : ml * EPI_PITCH;
 }
-// general form of the table GELU on the split table (gelu_lut's logic; tab = LDS base)
-MJV_DEV float gelu_lut_split(float xf, const char* lds) {
-  const unsigned u = __float_as_uint(xf);
-  const unsigned mag = (u >> 16) & 0x7fffu;
-  const unsigned rel = mag - MJV_GELU_LO;
-  const unsigned sgn = (unsigned)((int)u >> 31);
-  const bool in_tab = rel < (unsigned)MJV_GELU_R;
-  const unsigned t = *(const u16*)(lds + (sgn & G_NEG) + (in_tab ? rel * 2 : 0u));
-  const unsigned big = gelu_beyond_table(u, mag);               // beyond the table (mjv_common.h)
-  const unsigned small = __float_as_uint(0.5f * xf);
-  const unsigned other = mag < MJV_GELU_LO ? small : big;
-  return __uint_as_float(in_tab ? (t << 16) : other);
-}
-
-// per-lane global source pointers of the two 1-KiB DMA pieces a wave issues for each of the four half-tiles
-// (W rows 0-127, W rows 128-255, A rows 0-127, A rows 128-255) at k = 0: the row clamp and the chunk swizzle are loop
-// invariant, so a stage is two {pointer + k offset, global_load_lds} pairs - the DMA issue sits in the load segment that
-// has to hide under the partner wave's 16-MFMA segment
-struct StagePtrs {
-  const u16* src[4][2];
-};
-
-MJV_DEV void init_stage_ptrs(StagePtrs& sp, const GemmArgs& p, int m0, int n0, int wave, int lane) {
-#pragma unroll
-  for (int which = 0; which < 4; ++which) {
-    const bool is_w = which < 2;
-    const u16* base = is_w ? p.W : p.A;
-    const long ld = is_w ? p.ldw : p.lda;
-    const int row0 = (is_w ? n0 : m0) + (which & 1) * 128;
-    const int max_row = (is_w ? p.N : p.M) - 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = (wave * 2 + i) * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (r & 7);
-      int gr = row0 + r;
-      gr = gr < max_row ? gr : max_row;
-      sp.src[which][i] = base + (long)gr * ld + c * 8;
-    }
-  }
-}
-
+typedef HalfTilePtrs<u16> StagePtrs;
 // stage half-tile WHICH of K-tile t (no-op past the last K-tile)
 template <int WHICH, bool GL = false>
 MJV_DEV void stage_half(const StagePtrs& sp, int t, int nk, char* smem, int wave) {
@@ -600,13 +508,6 @@ MJV_DEV void stage_half(const StagePtrs& sp, int t, int nk, char* smem, int wave
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp.src[WHICH][i] + k0),
                                      (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
 }
-
-#define MJV_BARRIER()                      \
-  do {                                     \
-    __builtin_amdgcn_sched_barrier(0);     \
-    __builtin_amdgcn_s_barrier();          \
-    __builtin_amdgcn_sched_barrier(0);     \
-  } while (0)
 
 // VAR 0: production.  VAR 3 / 4: timing experiments (no epilogue / no global stores) used to attribute the epilogue's
 // cost; selected with mjv_gemm_set_tile(1000 + VAR), never by the automatic path.

@@ -25,17 +25,13 @@
 // every epilogue incl. the block quantiser) - mjv_gemm_mxfp8_dispatch plans it like gemm.hip plans the bf16 tails; (ii) the
 // GELU epilogue takes the split-table form of gemm.hip's round-4 pass A (G8_* below).
 #include "mx8.h"
-#include "gelu_table.h"
+#include "gemm_common.h"
 #include <atomic>
 
 namespace {
 
-__device__ const u16 g_gelu_table8[MJV_GELU_TABLE_LEN] = MJV_GELU_TABLE_INIT;   // (gemm.hip has its own copy: no -fgpu-rdc)
-
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 struct Gemm8Args {
   const uint8_t* A; long lda;        // e4m3 [M][lda]
@@ -55,36 +51,9 @@ struct Gemm8Args {
   float* ws; int split;              // K-sliced launches: fp32 accumulator images (gemm.hip's layout), slices per tile
 };
 
-MJV_DEV float silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-MJV_DEV unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-// general form of the table GELU (gemm.hip gelu_lut): x exactly representable in bf16
-MJV_DEV float gelu_lut(float xf, const u16* tab) {
-  const unsigned u = __float_as_uint(xf);
-  const unsigned mag = (u >> 16) & 0x7fffu;
-  const unsigned rel = mag - MJV_GELU_LO;
-  const unsigned sgn = (unsigned)((int)u >> 31);
-  const bool in_tab = rel < (unsigned)MJV_GELU_R;
-  const unsigned idx = in_tab ? rel + (sgn & MJV_GELU_NEG_OFF) : 0u;
-  const unsigned t = tab[idx];
-  const unsigned big = gelu_beyond_table(u, mag);               // beyond the table (mjv_common.h)
-  const unsigned small = __float_as_uint(0.5f * xf);
-  const unsigned other = mag < MJV_GELU_LO ? small : big;
-  return __uint_as_float(in_tab ? (t << 16) : other);
-}
-
-// XCD-aware tile order (gemm.hip tile_of_vblock): b-th of nwg tiles
+// XCD-aware tile order (gemm_common.h): b-th of nwg tiles
 MJV_DEV void tile_of_block(const Gemm8Args& p, const int nwg, const int b, int& tm, int& tn) {
-  const int GM = p.gm;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
-  const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
-  const int per_group = GM * p.tiles_n;
-  const int grp = t / per_group, in_grp = t - grp * per_group;
-  const int first_m = grp * GM;
-  const int gsz = min(p.tiles_m - first_m, GM);
-  tn = in_grp / gsz;
-  tm = first_m + (in_grp - tn * gsz);
+  xcd_tile_order(p.gm, p.tiles_m, p.tiles_n, nwg, b, tm, tn);
 }
 
 constexpr int BM = 256, BN = 256, BK = 128;   // BK in elements = bytes
@@ -103,7 +72,7 @@ static_assert(EPI_TILE_BYTES >= PIPE_BYTES && LDS_BYTES <= 160 * 1024 && SCALE_O
 // contiguous table took 9.  This kernel's pipeline owns bytes 0 .. 128 Ki during the main loop, so the table waits behind it
 // (where the prologue's DMA put it) and is moved to its two windows at the head of the epilogue (960 16-byte chunks, one barrier);
 // the staged output tile is split around the second window: rows 0 .. 108 between the windows, rows 109 .. 255 above.
-constexpr int G8_NEG = 65536;
+constexpr int G8_NEG = GELU_SPLIT_NEG;
 constexpr int G8_HALF = MJV_GELU_NEG_OFF * 2;                 // 7 680 bytes per sign half
 constexpr int G8_A0 = G8_HALF, G8_AROWS = (G8_NEG - G8_A0) / EPI_PITCH;
 constexpr int G8_B0 = G8_NEG + G8_HALF;
@@ -113,41 +82,7 @@ template <bool GL>
 MJV_DEV int erow8(int ml) {   // LDS byte offset of row ml of the staged output tile
   return GL ? ml * EPI_PITCH + (ml < G8_AROWS ? G8_A0 : G8_B0 - G8_AROWS * EPI_PITCH) : ml * EPI_PITCH;
 }
-// general form of the table GELU on the split table (gelu_lut's logic; lds = LDS base)
-MJV_DEV float gelu_lut_split8(float xf, const char* lds) {
-  const unsigned u = __float_as_uint(xf);
-  const unsigned mag = (u >> 16) & 0x7fffu;
-  const unsigned rel = mag - MJV_GELU_LO;
-  const unsigned sgn = (unsigned)((int)u >> 31);
-  const bool in_tab = rel < (unsigned)MJV_GELU_R;
-  const unsigned t = *(const u16*)(lds + (sgn & G8_NEG) + (in_tab ? rel * 2 : 0u));
-  const unsigned big = gelu_beyond_table(u, mag);
-  const unsigned small = __float_as_uint(0.5f * xf);
-  const unsigned other = mag < MJV_GELU_LO ? small : big;
-  return __uint_as_float(in_tab ? (t << 16) : other);
-}
-
-struct StagePtrs {
-  const uint8_t* src[4][2];
-};
-MJV_DEV void init_stage_ptrs(StagePtrs& sp, const Gemm8Args& p, int m0, int n0, int wave, int lane) {
-#pragma unroll
-  for (int which = 0; which < 4; ++which) {
-    const bool is_w = which < 2;
-    const uint8_t* base = is_w ? p.W : p.A;
-    const long ld = is_w ? p.ldw : p.lda;
-    const int row0 = (is_w ? n0 : m0) + (which & 1) * 128;
-    const int max_row = (is_w ? p.N : p.M) - 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = (wave * 2 + i) * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (r & 7);
-      int gr = row0 + r;
-      gr = gr < max_row ? gr : max_row;
-      sp.src[which][i] = base + (long)gr * ld + c * 16;
-    }
-  }
-}
+typedef HalfTilePtrs<uint8_t> StagePtrs;
 template <int WHICH>
 MJV_DEV void stage_half(const StagePtrs& sp, int t, int nk, char* smem, int wave) {
   if (t >= nk) return;
@@ -158,24 +93,6 @@ MJV_DEV void stage_half(const StagePtrs& sp, int t, int nk, char* smem, int wave
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sp.src[WHICH][i] + k0),
                                      (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
 }
-
-// streaming (nt) stores as inline assembly: `if (nt) __builtin_nontemporal_store(..) else plain` is merged into one PLAIN
-// store by hipcc (ROCm 7.2) - see gemm.hip store16
-MJV_DEV void store16(u16* dst, const u32x4& val, int nt) {
-  if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(val) : "memory");
-  else *(u32x4*)dst = val;
-}
-MJV_DEV void store8(uint8_t* dst, const u32x2& val, int nt) {
-  if (nt) asm volatile("global_store_dwordx2 %0, %1, off nt" ::"v"(dst), "v"(val) : "memory");
-  else *(u32x2*)dst = val;
-}
-
-#define MJV_BARRIER()                      \
-  do {                                     \
-    __builtin_amdgcn_sched_barrier(0);     \
-    __builtin_amdgcn_s_barrier();          \
-    __builtin_amdgcn_sched_barrier(0);     \
-  } while (0)
 
 template <int OA, int OB>
 MJV_DEV f32x4 mfma8(const i32x8& a, const i32x8& b, const f32x4& c, int sa, int sb) {
@@ -250,7 +167,7 @@ __global__ __launch_bounds__(512, 2) void gemm256f8_kernel(Gemm8Args p) {
     for (int i = 0; i < 2; ++i) {
       const int chunk = (i * 8 + wave) * 64 + lane;
       if (chunk < MJV_GELU_TABLE_LEN / 8)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const u32x4*)g_gelu_table8 + chunk),
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const u32x4*)g_gelu_table + chunk),
                                          (__attribute__((address_space(3))) void*)(smem + EPI_TILE_BYTES + (i * 8 + wave) * 1024), 16, 0, 0);
     }
   }
@@ -444,7 +361,7 @@ __global__ __launch_bounds__(512, 2) void gemm256f8_kernel(Gemm8Args p) {
           const int ml = wr * 128 + i * 16 + l15;
           float v[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_lut_split8(__uint_as_float(ubs[i][r]), smem);
+          for (int r = 0; r < 4; ++r) v[r] = gelu_lut_split(__uint_as_float(ubs[i][r]), smem);
           const u32x2 o = {pack2(v[0], v[1]), pack2(v[2], v[3])};
           *(u32x2*)(etile + erow8<GL>(ml) + nl * 2) = o;
         }
@@ -571,7 +488,7 @@ __global__ __launch_bounds__(256) void splitk_finish256f8_kernel(Gemm8Args p) {
     for (int e = 0; e < 8; ++e) v[e] = fr[e >> 2][e & 3] + b[e];
     if constexpr (EPI == MJV_EPI_BIAS_GELU) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = gelu_lut(rbf(v[e]), g_gelu_table8);
+      for (int e = 0; e < 8; ++e) v[e] = gelu_lut(rbf(v[e]), g_gelu_table);
     }
     if constexpr (EPI == MJV_EPI_BIAS_RELU) {
 #pragma unroll

@@ -10,7 +10,8 @@ typedef uint16_t u16;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -26,12 +27,13 @@ MJV_DEV u16 f2bf(float f) {
 }
 // round an fp32 value through bf16 (a torch op boundary in the reference's bf16 path): ONE v_cvt_pk_bf16_f32 with the value
 // in the HIGH half and zero in the low half - the packed word is the rounded value's fp32 bit pattern, no shift / mask
-typedef __attribute__((ext_vector_type(2))) float mjv_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 mjv_bf16x2;
 MJV_DEV float rbf(float f) {
-  return __builtin_bit_cast(float, __builtin_convertvector(mjv_f32x2{0.f, f}, mjv_bf16x2));
+  return __builtin_bit_cast(float, __builtin_convertvector(f32x2{0.f, f}, bf16x2));
 }
 MJV_DEV unsigned pack2bf(float lo, float hi) { return (unsigned)f2bf(lo) | ((unsigned)f2bf(hi) << 16); }
+// two fp32 -> packed bf16 pair in one v_cvt_pk_bf16_f32
+MJV_DEV unsigned pack2(f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); }
+MJV_DEV unsigned pack2(float lo, float hi) { return pack2(f32x2{lo, hi}); }
 
 // GELU of a bf16 value whose magnitude lies past the table (|x| >= 128), as torch's CPU bf16 kernel returns it (x * 0.5 * (1 + erf)
 // in fp32, rounded): x for finite x > 0 until 2 x overflows fp32 (bf16 patterns 0x7f00..0x7f7f -> +inf), -0 for finite x < 0, NaN

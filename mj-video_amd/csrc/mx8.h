@@ -30,10 +30,10 @@ MJV_DEV u32x2 mx8_cvt8(const u32x4& v, float scale) {
   // (ROCm 7.2) convert v[0] four times)
   const unsigned e0 = v[0], e1 = v[1], e2 = v[2], e3 = v[3];
   mx8_s16x2 lo = {0, 0}, hi = {0, 0};
-  lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_bit_cast(mjv_bf16x2, e0), scale, false);
-  lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_bit_cast(mjv_bf16x2, e1), scale, true);
-  hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_bit_cast(mjv_bf16x2, e2), scale, false);
-  hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_bit_cast(mjv_bf16x2, e3), scale, true);
+  lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_bit_cast(bf16x2, e0), scale, false);
+  lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(lo, __builtin_bit_cast(bf16x2, e1), scale, true);
+  hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_bit_cast(bf16x2, e2), scale, false);
+  hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_bit_cast(bf16x2, e3), scale, true);
   return u32x2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
 }
 // byte offset of the scale of (row, 32-element block starting at column col) inside a scale buffer with `groups` 64-row groups

@@ -2,6 +2,7 @@
 // patchify (im2col), CLS rows, token-embedding gather.  One 64-lane wave per row, 16-byte accesses.
 #include "mjv_common.h"
 #include <algorithm>
+#include <type_traits>
 #include "mx8.h"
 
 namespace {
@@ -9,14 +10,73 @@ namespace {
 constexpr int WAVES = 4;          // rows per 256-thread workgroup
 constexpr int MAX_IT = 8;         // 8 chunks of 512 elements -> rows up to 4096 wide
 
+// ------------------------------------------------------------------------------------------ row helpers
+// A lane's part of a row: chunk `it` is 8 elements, 512 columns after chunk it - 1 (lanes side by side); fn(it, column) runs for the
+// chunks inside the row.  IT = chunks a lane covers (row width <= 512 * IT): the narrower instantiations keep fewer values in
+// registers, so more rows are in flight per CU.  (Unrolled by recursion, not a loop: the chunk index is a constant wherever a
+// body is inlined, which keeps the register counts of the bodies written out in place.)
+template <int IT, int it = 0, class F>
+MJV_DEV void for_row_chunks(int dim, int lane, F&& fn) {
+  if constexpr (it < IT) {
+    const int c = it * 512 + lane * 8;
+    if (c < dim) fn(it, c);
+    for_row_chunks<IT, it + 1>(dim, lane, fn);
+  }
+}
+
+// The row statistics.  load(it, c) fills v[it] with the fp32 values of chunk it; they are summed as they arrive.  Accumulation
+// order (a folded norm and an unfolded one must agree bit for bit): per lane, chunks ascending, elements 0..7 ascending, then
+// wave_sum.
+template <int IT, class L>
+MJV_DEV float row_sum_squares(float (&v)[IT][8], int dim, int lane, L&& load) {
+  float sq = 0.f;
+  for_row_chunks<IT>(dim, lane, [&](int it, int c) {
+    load(it, c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sq += v[it][j] * v[it][j];
+  });
+  return wave_sum(sq);
+}
+// two-pass: the mean, then the sum of squares of the centred values (returned)
+template <int IT, class L>
+MJV_DEV float row_mean_centred_squares(float (&v)[IT][8], int dim, int lane, float& mean, L&& load) {
+  float sum = 0.f, sq = 0.f;
+  for_row_chunks<IT>(dim, lane, [&](int it, int c) {
+    load(it, c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += v[it][j];
+  });
+  const float m = mean = wave_sum(sum) / (float)dim;
+  for_row_chunks<IT>(dim, lane, [&](int it, int) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = v[it][j] - m;
+      sq += d * d;
+    }
+  });
+  return wave_sum(sq);
+}
+
+// Output tail of the norms: 8 results of (row, columns c .. c + 7) as bf16, or - MX8 - block-quantised on the way out (y = e4m3
+// bytes, ldy in bytes, ys = scale records; include/mjv.h "MXFP8 operand format"): the input of an fp8 GEMM.  A lane's 8 columns
+// are a quarter of a 32-element block (dim % 128 == 0: whole quads are inside the row).
+template <bool MX8>
+MJV_DEV void store_chunk(u16* y, long ldy, int row, int c, int lane, const float* o, uint8_t* ys, long groups) {
+  if constexpr (MX8) {
+    unsigned sb;
+    const u32x2 q = mx8_quantize_quad(pack8(o), sb);
+    *(u32x2*)((uint8_t*)y + (long)row * ldy + c) = q;
+    if ((lane & 3) == 0) ys[mx8_scale_offset(row, c, groups)] = (uint8_t)sb;
+  } else {
+    *(u32x4*)(y + (long)row * ldy + c) = pack8(o);
+  }
+}
+
 // ---------------------------------------------------------------------------------------- LayerNorm
 // nn.LayerNorm on a bf16 tensor: fp32 mean / biased variance, y = bf16((x - mean) * rstd * g + b).
 // gather_grid > 0: the logical input row is the concatenation of 4 rows of the ViT output (pixel shuffle,
 // modeling_internvl_chat.py:228-242): out token (tile, a2, b2) <- rows (2a2,2b2) (2a2,2b2+1) (2a2+1,2b2) (2a2+1,2b2+1).
-// IT = chunks of 512 elements a lane group covers (row width <= 512 * IT): the narrower instantiations keep fewer values
-// in registers, so more rows are in flight per CU.
-// MX8: the bf16 result is block-quantised on the way out (y = e4m3 bytes, ldy in bytes, ys = scale records; include/mjv.h
-// "MXFP8 operand format"): the input of the fp8 fc1 GEMM.  A lane's 8 columns are a quarter of a 32-element block.
+// MX8: store_chunk<true>, the input of the fp8 fc1 GEMM.
 template <int IT, bool MX8 = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const u16* __restrict__ x, long ldx, u16* __restrict__ y, long ldy,
                                                         const u16* __restrict__ gamma, const u16* __restrict__ beta,
@@ -39,63 +99,34 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const u16* __restrict__ 
     src_base[3] = (tb + (2 * a2 + 1) * grid + 2 * b2 + 1) * ldx;
   }
   float v[IT][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-      const u16* src;
-      if (grid > 0) {
-        const int qd = c / quarter;
-        src = x + src_base[qd] + (c - qd * quarter);
-      } else {
-        src = x + (long)row * ldx + c;
-      }
-      unpack8(*(const u32x4*)src, v[it]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sum += v[it][j];
+  const auto load = [&](int it, int c) {
+    const u16* src;
+    if (grid > 0) {
+      const int qd = c / quarter;
+      src = x + src_base[qd] + (c - qd * quarter);
+    } else {
+      src = x + (long)row * ldx + c;
     }
-  }
-  const float mean = wave_sum(sum) / (float)dim;
-  float sq = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = v[it][j] - mean;
-        sq += d * d;
-      }
-    }
-  }
-  const float var = wave_sum(sq) / (float)dim;
+    unpack8(*(const u32x4*)src, v[it]);
+  };
+  float mean;
+  const float var = row_mean_centred_squares<IT>(v, dim, lane, mean, load) / (float)dim;
   const float rstd = rsqrtf(var + eps);
+  for_row_chunks<IT>(dim, lane, [&](int it, int c) {
+    float g[8], b[8], o[8];
+    unpack8(*(const u32x4*)(gamma + c), g);
+    unpack8(*(const u32x4*)(beta + c), b);
 #pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-      float g[8], b[8], o[8];
-      unpack8(*(const u32x4*)(gamma + c), g);
-      unpack8(*(const u32x4*)(beta + c), b);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (v[it][j] - mean) * rstd * g[j] + b[j];
-      if constexpr (MX8) {
-        unsigned sb;
-        const u32x2 q = mx8_quantize_quad(pack8(o), sb);   // (dim % 128 == 0: whole quads are inside the row)
-        *(u32x2*)((uint8_t*)y + (long)row * ldy + c) = q;
-        if ((lane & 3) == 0) ys[mx8_scale_offset(row, c, groups)] = (uint8_t)sb;
-      } else {
-        *(u32x4*)(y + (long)row * ldy + c) = pack8(o);
-      }
-    }
-  }
+    for (int j = 0; j < 8; ++j) o[j] = (v[it][j] - mean) * rstd * g[j] + b[j];
+    store_chunk<MX8>(y, ldy, row, c, lane, o, ys, groups);
+  });
 }
 
 // ------------------------------------------------------------------------------------------ RMSNorm
 // modeling_internlm2.py:138-143: h = bf16(x32 * rsqrt(mean(x32^2) + eps)); y = bf16(w * h)
 // PARTS > 0 (bench build only, the A/B of DESIGN "Norm fusion"): the row's sum of squares arrives as PARTS per-n-tile partial
 // sums from the producing GEMM's epilogue ([rows][PARTS] fp32, summed here in tile order) instead of being reduced in here
+// MX8: store_chunk<true>, the input of the fp8 w1|w3 GEMM.
 template <int IT, int PARTS = 0, bool MX8 = false>
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* __restrict__ x, long ldx, u16* __restrict__ y, long ldy,
                                                       const u16* __restrict__ w, const int* __restrict__ row_index,
@@ -106,44 +137,23 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const u16* __restrict__ x,
   if (row >= rows) return;
   const long srow = row_index ? row_index[row] : row;
   float v[IT][8];
-  float sq = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-      unpack8(*(const u32x4*)(x + srow * ldx + c), v[it]);
-      if constexpr (PARTS == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sq += v[it][j] * v[it][j];
-      }
-    }
-  }
+  const auto load = [&](int it, int c) { unpack8(*(const u32x4*)(x + srow * ldx + c), v[it]); };
   float total;
-  if constexpr (PARTS == 0) total = wave_sum(sq);
+  if constexpr (PARTS == 0) total = row_sum_squares<IT>(v, dim, lane, load);
   else {
+    for_row_chunks<IT>(dim, lane, load);
     total = 0.f;
 #pragma unroll
     for (int t = 0; t < PARTS; ++t) total += partials[srow * PARTS + t];
   }
   const float rstd = rsqrtf(total / (float)dim + eps);
+  for_row_chunks<IT>(dim, lane, [&](int it, int c) {
+    float g[8], o[8];
+    unpack8(*(const u32x4*)(w + c), g);
 #pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-      float g[8], o[8];
-      unpack8(*(const u32x4*)(w + c), g);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = g[j] * rbf(v[it][j] * rstd);
-      if constexpr (MX8) {   // (see layernorm_kernel: the input of the fp8 w1|w3 GEMM)
-        unsigned sb;
-        const u32x2 q = mx8_quantize_quad(pack8(o), sb);
-        *(u32x2*)((uint8_t*)y + (long)row * ldy + c) = q;
-        if ((lane & 3) == 0) ys[mx8_scale_offset(row, c, groups)] = (uint8_t)sb;
-      } else {
-        *(u32x4*)(y + (long)row * ldy + c) = pack8(o);
-      }
-    }
-  }
+    for (int j = 0; j < 8; ++j) o[j] = g[j] * rbf(v[it][j] * rstd);
+    store_chunk<MX8>(y, ldy, row, c, lane, o, ys, groups);
+  });
 }
 
 // ------------------------------------------------------------------------------------------ row statistics
@@ -157,35 +167,10 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const u16* __restrict__ 
   const int row = blockIdx.x * WAVES + (threadIdx.x >> 6);
   if (row >= rows) return;
   float v[IT][8];
-  float sum = 0.f, sq = 0.f;
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int c = it * 512 + lane * 8;
-    if (c < dim) {
-      unpack8(*(const u32x4*)(x + (long)row * ldx + c), v[it]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if constexpr (MEAN) sum += v[it][j];
-        else sq += v[it][j] * v[it][j];
-      }
-    }
-  }
+  const auto load = [&](int it, int c) { unpack8(*(const u32x4*)(x + (long)row * ldx + c), v[it]); };
   float mean = 0.f;
-  if constexpr (MEAN) {
-    mean = wave_sum(sum) / (float)dim;
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int c = it * 512 + lane * 8;
-      if (c < dim) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = v[it][j] - mean;
-          sq += d * d;
-        }
-      }
-    }
-  }
-  const float r = rsqrtf(wave_sum(sq) / (float)dim + eps);
+  const float sq = MEAN ? row_mean_centred_squares<IT>(v, dim, lane, mean, load) : row_sum_squares<IT>(v, dim, lane, load);
+  const float r = rsqrtf(sq / (float)dim + eps);
   if (lane == 0) {
     rstd[row] = r;
     if constexpr (MEAN) mean_rstd[row] = mean * r;
@@ -193,6 +178,25 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const u16* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------- RoPE + GQA de-interleave
+// One thread's rotary step: the 8 elements at src and their partners `half` elements on, x' = bf16(bf16(x cos) +
+// bf16(rotate_half(x) sin)) with the bf16 table rows cos_row / sin_row (this thread's 8 columns, partners `half` on), to dst.
+MJV_DEV void rotate8(const u16* src, u16* dst, int half, const u16* cos_row, const u16* sin_row) {
+  float x1[8], x2[8], c1[8], c2[8], s1[8], s2[8], o1[8], o2[8];
+  unpack8(*(const u32x4*)src, x1);
+  unpack8(*(const u32x4*)(src + half), x2);
+  unpack8(*(const u32x4*)cos_row, c1);
+  unpack8(*(const u32x4*)(cos_row + half), c2);
+  unpack8(*(const u32x4*)sin_row, s1);
+  unpack8(*(const u32x4*)(sin_row + half), s2);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    o1[j] = rbf(x1[j] * c1[j]) + rbf(-x2[j] * s1[j]);
+    o2[j] = rbf(x2[j] * c2[j]) + rbf(x1[j] * s2[j]);
+  }
+  *(u32x4*)dst = pack8(o1);
+  *(u32x4*)(dst + half) = pack8(o2);
+}
+
 // wqkv output columns are (kv_head, [q_0 .. q_{g-1}, k, v], 128)  (modeling_internlm2.py:361-371).
 // q' = bf16(bf16(q*cos) + bf16(rotate_half(q)*sin)) with bf16 tables (modeling_internlm2.py:240-247).
 // One thread: 8 elements d..d+7 of the first half and their partners d+64..d+71 of one (row, head slot).
@@ -212,20 +216,7 @@ __global__ __launch_bounds__(256) void rope_split_kernel(const u16* __restrict__
   const u16* src = qkv + row * ldqkv + ((long)kvh * (group + 2) + within) * 128;
   u16* dst = (within < group) ? q + row * ldq + ((long)kvh * group + within) * 128 : k + row * ldk + (long)kvh * 128;
   const long pos = positions[row];
-  float x1[8], x2[8], c1[8], c2[8], s1[8], s2[8], o1[8], o2[8];
-  unpack8(*(const u32x4*)(src + d), x1);
-  unpack8(*(const u32x4*)(src + d + 64), x2);
-  unpack8(*(const u32x4*)(cos_tab + pos * 128 + d), c1);
-  unpack8(*(const u32x4*)(cos_tab + pos * 128 + d + 64), c2);
-  unpack8(*(const u32x4*)(sin_tab + pos * 128 + d), s1);
-  unpack8(*(const u32x4*)(sin_tab + pos * 128 + d + 64), s2);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    o1[j] = rbf(x1[j] * c1[j]) + rbf(-x2[j] * s1[j]);
-    o2[j] = rbf(x2[j] * c2[j]) + rbf(x1[j] * s2[j]);
-  }
-  *(u32x4*)(dst + d) = pack8(o1);
-  *(u32x4*)(dst + d + 64) = pack8(o2);
+  rotate8(src + d, dst + d, 64, cos_tab + pos * 128 + d, sin_tab + pos * 128 + d);
 }
 
 // Rotary embedding IN PLACE on n_heads consecutive heads of every row (the Phi-3 layout of BASELINE configs[4]'s language
@@ -246,20 +237,7 @@ __global__ __launch_bounds__(256) void rope_heads_kernel(u16* __restrict__ x, lo
   const long row = rh / n_heads;
   u16* p = x + row * ldx + (long)head * head_stride;
   const long pos = positions[row];
-  float x1[8], x2[8], c1[8], c2[8], s1[8], s2[8], o1[8], o2[8];
-  unpack8(*(const u32x4*)(p + d), x1);
-  unpack8(*(const u32x4*)(p + d + half), x2);
-  unpack8(*(const u32x4*)(cos_tab + pos * rot_dim + d), c1);
-  unpack8(*(const u32x4*)(cos_tab + pos * rot_dim + d + half), c2);
-  unpack8(*(const u32x4*)(sin_tab + pos * rot_dim + d), s1);
-  unpack8(*(const u32x4*)(sin_tab + pos * rot_dim + d + half), s2);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    o1[j] = rbf(x1[j] * c1[j]) + rbf(-x2[j] * s1[j]);
-    o2[j] = rbf(x2[j] * c2[j]) + rbf(x1[j] * s2[j]);
-  }
-  *(u32x4*)(p + d) = pack8(o1);
-  *(u32x4*)(p + d + half) = pack8(o2);
+  rotate8(p + d, p + d, half, cos_tab + pos * rot_dim + d, sin_tab + pos * rot_dim + d);
 }
 
 // --------------------------------------------------------------------------------------------- patchify
@@ -300,107 +278,101 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const int* __restrict
   for (int c = threadIdx.x * 8; c < dim; c += blockDim.x * 8) *(u32x4*)(x + (long)row * ldx + c) = *(const u32x4*)(src + c);
 }
 
+// ------------------------------------------------------------------------------------------ norm entries
+// What the five norm entries share: the supported widths, one wave per row, IT by width.
+bool norm_dims_ok(const char* entry, int rows, int dim, int dim_multiple) {
+  if (rows > 0 && dim > 0 && dim % dim_multiple == 0 && dim <= 512 * MAX_IT) return true;
+  mjv_set_error("%s: dim %d unsupported", entry, dim);
+  return false;
+}
+// launch(grid, IT as a std::integral_constant)
+template <class F>
+int launch_rows(const char* entry, int rows, int dim, F&& launch) {
+  const dim3 grid((rows + WAVES - 1) / WAVES);
+  if (dim <= 1024) launch(grid, std::integral_constant<int, 2>{});
+  else if (dim <= 2048) launch(grid, std::integral_constant<int, 4>{});
+  else launch(grid, std::integral_constant<int, MAX_IT>{});
+  return mjv_check_launch(entry);
+}
+
 }  // namespace
 
 extern "C" int mjv_layernorm_bf16(const mjv_bf16* x, int64_t ldx, mjv_bf16* y, int64_t ldy, const mjv_bf16* gamma,
                                   const mjv_bf16* beta, int32_t rows, int32_t dim, float eps, int32_t gather_grid,
                                   void* stream) {
   MJV_REQUIRE(x && y && gamma && beta, "layernorm: null pointer");
-  MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "layernorm: dim %d unsupported", dim);
+  if (!norm_dims_ok("layernorm", rows, dim, 8)) return MJV_E_ARG;
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "layernorm: ld alignment");
   MJV_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0,
               "layernorm: alignment (16-byte pieces of a row: x, y, gamma, beta must be 16-byte aligned)");
   if (gather_grid > 0) MJV_REQUIRE(gather_grid % 2 == 0 && dim % 32 == 0, "layernorm: gather needs an even grid");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps(gather_grid > 0 ? "layernorm_pixshuf" : "layernorm", s, 0, 4.0 * rows * (double)dim);
-  const dim3 grid((rows + WAVES - 1) / WAVES);
-  if (dim <= 1024)
-    hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, gamma, beta, rows, dim, eps, gather_grid);
-  else if (dim <= 2048)
-    hipLaunchKernelGGL(layernorm_kernel<4>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, gamma, beta, rows, dim, eps, gather_grid);
-  else
-    hipLaunchKernelGGL(layernorm_kernel<MAX_IT>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, gamma, beta, rows, dim, eps, gather_grid);
-  return mjv_check_launch("layernorm");
+  return launch_rows("layernorm", rows, dim, [&](dim3 grid, auto it) {
+    hipLaunchKernelGGL(layernorm_kernel<decltype(it)::value>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, gamma, beta, rows, dim,
+                       eps, gather_grid);
+  });
 }
 
 extern "C" int mjv_rmsnorm_bf16(const mjv_bf16* x, int64_t ldx, mjv_bf16* y, int64_t ldy, const mjv_bf16* w,
                                 const int32_t* row_index, int32_t rows, int32_t dim, float eps, void* stream) {
   MJV_REQUIRE(x && y && w, "rmsnorm: null pointer");
-  MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "rmsnorm: dim %d unsupported", dim);
+  if (!norm_dims_ok("rmsnorm", rows, dim, 8)) return MJV_E_ARG;
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "rmsnorm: ld alignment");
   MJV_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) % 16 == 0,
               "rmsnorm: alignment (16-byte pieces of a row: x, y, w must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("rmsnorm", s, 0, 4.0 * rows * (double)dim);
-  const dim3 grid((rows + WAVES - 1) / WAVES);
-  if (dim <= 1024)
-    hipLaunchKernelGGL(rmsnorm_kernel<2>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, w, row_index, rows, dim, eps);
-  else if (dim <= 2048)
-    hipLaunchKernelGGL(rmsnorm_kernel<4>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, w, row_index, rows, dim, eps);
-  else
-    hipLaunchKernelGGL(rmsnorm_kernel<MAX_IT>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, w, row_index, rows, dim, eps);
-  return mjv_check_launch("rmsnorm");
+  return launch_rows("rmsnorm", rows, dim, [&](dim3 grid, auto it) {
+    hipLaunchKernelGGL(rmsnorm_kernel<decltype(it)::value>, grid, dim3(256), 0, s, x, (long)ldx, y, (long)ldy, w, row_index, rows, dim, eps);
+  });
 }
 
 extern "C" int mjv_row_stats_bf16(const mjv_bf16* x, int64_t ldx, float* rstd, float* mean_rstd, int32_t rows, int32_t dim, float eps,
                                   void* stream) {
   MJV_REQUIRE(x && rstd, "row_stats: null pointer");
-  MJV_REQUIRE(rows > 0 && dim > 0 && dim % 8 == 0 && dim <= 512 * MAX_IT, "row_stats: dim %d unsupported", dim);
+  if (!norm_dims_ok("row_stats", rows, dim, 8)) return MJV_E_ARG;
   MJV_REQUIRE(ldx % 8 == 0 && (uintptr_t)x % 16 == 0, "row_stats: alignment (16-byte pieces of a row: ldx % 8, x 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps(mean_rstd ? "row_stats_ln" : "row_stats_rms", s, 0, 2.0 * rows * (double)dim);
-  const dim3 grid((rows + WAVES - 1) / WAVES);
-#define MJV_RS(IT)                                                                                                               \
-  do {                                                                                                                           \
-    if (mean_rstd) hipLaunchKernelGGL((row_stats_kernel<IT, true>), grid, dim3(256), 0, s, x, (long)ldx, rstd, mean_rstd, rows, dim, eps); \
-    else hipLaunchKernelGGL((row_stats_kernel<IT, false>), grid, dim3(256), 0, s, x, (long)ldx, rstd, mean_rstd, rows, dim, eps);         \
-  } while (0)
-  if (dim <= 1024) MJV_RS(2);
-  else if (dim <= 2048) MJV_RS(4);
-  else MJV_RS(MAX_IT);
-#undef MJV_RS
-  return mjv_check_launch("row_stats");
+  return launch_rows("row_stats", rows, dim, [&](dim3 grid, auto it) {
+    constexpr int IT = decltype(it)::value;
+    if (mean_rstd) hipLaunchKernelGGL((row_stats_kernel<IT, true>), grid, dim3(256), 0, s, x, (long)ldx, rstd, mean_rstd, rows, dim, eps);
+    else hipLaunchKernelGGL((row_stats_kernel<IT, false>), grid, dim3(256), 0, s, x, (long)ldx, rstd, mean_rstd, rows, dim, eps);
+  });
 }
 
 extern "C" int mjv_layernorm_mxfp8(const mjv_bf16* x, int64_t ldx, uint8_t* y, int64_t ldy, uint8_t* y_scales, const mjv_bf16* gamma,
                                    const mjv_bf16* beta, int32_t rows, int32_t dim, float eps, void* stream) {
   MJV_REQUIRE(x && y && y_scales && gamma && beta, "layernorm_mxfp8: null pointer");
-  MJV_REQUIRE(rows > 0 && dim > 0 && dim % 128 == 0 && dim <= 512 * MAX_IT, "layernorm_mxfp8: dim %d unsupported", dim);
+  if (!norm_dims_ok("layernorm_mxfp8", rows, dim, 128)) return MJV_E_ARG;
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (uintptr_t)y % 8 == 0, "layernorm_mxfp8: alignment");
   MJV_REQUIRE(((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0,
               "layernorm_mxfp8: alignment (x, gamma, beta must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("layernorm_mxfp8", s, 0, 3.03 * rows * (double)dim);
-  const dim3 grid((rows + WAVES - 1) / WAVES);
   const long groups = (rows + 63) / 64;
-  if (dim <= 1024)
-    hipLaunchKernelGGL((layernorm_kernel<2, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, gamma, beta, rows, dim, eps, 0, y_scales, groups);
-  else if (dim <= 2048)
-    hipLaunchKernelGGL((layernorm_kernel<4, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, gamma, beta, rows, dim, eps, 0, y_scales, groups);
-  else
-    hipLaunchKernelGGL((layernorm_kernel<MAX_IT, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, gamma, beta, rows, dim, eps, 0, y_scales, groups);
-  return mjv_check_launch("layernorm_mxfp8");
+  return launch_rows("layernorm_mxfp8", rows, dim, [&](dim3 grid, auto it) {
+    hipLaunchKernelGGL((layernorm_kernel<decltype(it)::value, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, gamma, beta,
+                       rows, dim, eps, 0, y_scales, groups);
+  });
 }
 
 extern "C" int mjv_rmsnorm_mxfp8(const mjv_bf16* x, int64_t ldx, uint8_t* y, int64_t ldy, uint8_t* y_scales, const mjv_bf16* w,
                                  int32_t rows, int32_t dim, float eps, void* stream) {
   MJV_REQUIRE(x && y && y_scales && w, "rmsnorm_mxfp8: null pointer");
-  MJV_REQUIRE(rows > 0 && dim > 0 && dim % 128 == 0 && dim <= 512 * MAX_IT, "rmsnorm_mxfp8: dim %d unsupported", dim);
+  if (!norm_dims_ok("rmsnorm_mxfp8", rows, dim, 128)) return MJV_E_ARG;
   MJV_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (uintptr_t)y % 8 == 0, "rmsnorm_mxfp8: alignment");
   MJV_REQUIRE(((uintptr_t)x | (uintptr_t)w) % 16 == 0, "rmsnorm_mxfp8: alignment (x, w must be 16-byte aligned)");
   hipStream_t s = (hipStream_t)stream;
   MjvProfScope ps("rmsnorm_mxfp8", s, 0, 3.03 * rows * (double)dim);
-  const dim3 grid((rows + WAVES - 1) / WAVES);
   const long groups = (rows + 63) / 64;
   const int* no_index = nullptr;
   const float* no_parts = nullptr;
-  if (dim <= 1024)
-    hipLaunchKernelGGL((rmsnorm_kernel<2, 0, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, w, no_index, rows, dim, eps, no_parts, y_scales, groups);
-  else if (dim <= 2048)
-    hipLaunchKernelGGL((rmsnorm_kernel<4, 0, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, w, no_index, rows, dim, eps, no_parts, y_scales, groups);
-  else
-    hipLaunchKernelGGL((rmsnorm_kernel<MAX_IT, 0, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, w, no_index, rows, dim, eps, no_parts, y_scales, groups);
-  return mjv_check_launch("rmsnorm_mxfp8");
+  return launch_rows("rmsnorm_mxfp8", rows, dim, [&](dim3 grid, auto it) {
+    hipLaunchKernelGGL((rmsnorm_kernel<decltype(it)::value, 0, true>), grid, dim3(256), 0, s, x, (long)ldx, (u16*)y, (long)ldy, w, no_index,
+                       rows, dim, eps, no_parts, y_scales, groups);
+  });
 }
 
 #ifdef MJV_BENCH
@@ -421,16 +393,15 @@ extern "C" int mjv_bench_rmsnorm_prestat(const mjv_bf16* x, int64_t ldx, mjv_bf1
 // HBM-bound kernel - 16-byte loads and stores, a grid of one wave's worth of rows per workgroup pass, the GELU table in LDS.
 //   kind 1: y = gelu(bf16(x + bias))              (fc1)
 //   kind 3: y = res + bf16(bf16(x + bias) * scale)   (proj / fc2; scale NULL: y = res + bf16(x + bias); bias NULL: wo / w2)
-#include "gelu_table.h"
+#include "gemm_common.h"
 namespace {
-__device__ const u16 g_gelu_table_pass[MJV_GELU_TABLE_LEN] = MJV_GELU_TABLE_INIT;
 template <int KIND>
 __global__ __launch_bounds__(256) void epilogue_pass_kernel(const u16* __restrict__ x, long ldx, u16* __restrict__ y, long ldy,
                                                             const u16* __restrict__ bias, const u16* __restrict__ scale,
                                                             const u16* __restrict__ res, long ldr, int rows, int cols) {
   __shared__ u16 tab[KIND == 1 ? MJV_GELU_TABLE_LEN : 8];
   if constexpr (KIND == 1) {
-    for (int i = threadIdx.x; i < MJV_GELU_TABLE_LEN / 8; i += 256) ((u32x4*)tab)[i] = ((const u32x4*)g_gelu_table_pass)[i];
+    for (int i = threadIdx.x; i < MJV_GELU_TABLE_LEN / 8; i += 256) ((u32x4*)tab)[i] = ((const u32x4*)g_gelu_table)[i];
     __syncthreads();
   }
   const int cpr = cols / 8;                       // 16-byte chunks per row
@@ -445,14 +416,7 @@ __global__ __launch_bounds__(256) void epilogue_pass_kernel(const u16* __restric
     for (int e = 0; e < 8; ++e) v[e] = rbf(v[e] + b[e]);
     if constexpr (KIND == 1) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const unsigned u = __float_as_uint(v[e]);
-        const unsigned mag = (u >> 16) & 0x7fffu, rel = mag - MJV_GELU_LO;
-        const bool in_tab = rel < (unsigned)MJV_GELU_R;
-        const unsigned t = tab[in_tab ? rel + (u >> 31) * MJV_GELU_NEG_OFF : 0u];
-        const unsigned other = mag < MJV_GELU_LO ? __float_as_uint(0.5f * v[e]) : gelu_beyond_table(u, mag);
-        v[e] = __uint_as_float(in_tab ? (t << 16) : other);
-      }
+      for (int e = 0; e < 8; ++e) v[e] = gelu_lut(v[e], tab);
     } else {
       float r[8], sc[8];
       unpack8(__builtin_nontemporal_load((const u32x4*)(res + row * ldr + col)), r);
