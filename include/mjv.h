@@ -35,6 +35,9 @@
  * ABI 7, additive (MJV_ABI_VERSION stays 7: nothing existing changes): mjv_attention_ctx_bf16 with its plan / workspace queries -
  * causal attention of few own rows per sequence over long key / value contexts that many sequences share (the caption pass of
  * model.score_captions).
+ * ABI 7, additive (MJV_ABI_VERSION stays 7, no new symbol): one field at the END of mjv_attn_ctx_desc, ctx_any_length - 0 = as
+ * before (a context is a positive multiple of 64 keys), 1 = a context may end at any key, so a caller can cache the whole
+ * prefix that the captions of a video share.
  */
 #ifndef MJV_H_
 #define MJV_H_
@@ -225,7 +228,10 @@ int mjv_attention_bf16(const mjv_attn_desc* d, void* stream);
  *   Q / K / V / O : the own rows, addressed as in mjv_attn_desc - cu_seqlens: K / V rows; cu_seqlens_q, optional: the queries are
  *       the LAST cu_seqlens_q[s + 1] - cu_seqlens_q[s] own rows, packed at those rows of Q / O.
  *   ctx_k / ctx_v : every context's rows in one packed buffer each, with leading dimensions and head strides of their own;
- *       a context's length is a positive multiple of 64.  Or ctx_k_list / ctx_v_list (end of the struct): one base pointer per
+ *       a context's length is a positive multiple of 64, or (ctx_any_length = 1) any positive length: a context of `len` keys
+       then has ceil(len / 64) key tiles, its last piece ends at `len` and masks the keys behind it as an own part does; rows
+       behind a context's length are NEVER READ (they need not exist).  For lengths that are multiples of 64 the plan, the
+       workspace and every bit of the result are those of ctx_any_length = 0.  Or ctx_k_list / ctx_v_list (end of the struct): one base pointer per
  *       context, no packed buffer.
  *   cu_seqlens / cu_seqlens_q / context_index / cu_context are HOST arrays, read during the call only: every shape is checked
  *       on the host before anything is launched.  What the kernels read is the PLAN, a device copy of the int32 array
@@ -269,6 +275,10 @@ typedef struct mjv_attn_ctx_desc {
    * and every bit of the result.  The entry cannot read the arrays: what they hold is the caller's to check. */
   const mjv_bf16* const* ctx_k_list;
   const mjv_bf16* const* ctx_v_list;
+  /* 0 = every context is a positive multiple of 64 keys (anything else: MJV_E_ARG); 1 = any positive length.  Other values:
+   * MJV_E_ARG.  In the packed buffers a context's rows start at cu_context[c] as before; a listed context tensor holds at least
+   * cu_context[c + 1] - cu_context[c] rows. */
+  int32_t ctx_any_length;
 } mjv_attn_ctx_desc;
 
 /* Reads the index arrays and sizes of `d` only (no device pointer).  plan_host == NULL: returns the number of int32 the plan

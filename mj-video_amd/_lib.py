@@ -69,6 +69,42 @@ class AttnCtxDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
                 # per-context base pointers (DEVICE arrays [n_contexts]; both NULL = the packed ctx_k / ctx_v)
                 ("ctx_k_list", C.c_void_p), ("ctx_v_list", C.c_void_p)]
+    # ``_fields_`` is the descriptor up to the per-context lists and stays that list: code that enumerates it keeps seeing the
+    # layout it knows.  What mjv.h appends behind ``ctx_v_list`` lives in the instance's TAIL - the buffer is grown to the C
+    # struct's size on construction and a property reads / writes the field at its C offset:
+    #   int32_t ctx_any_length   1 = a context may have any positive length; 0 (a fresh descriptor) = a positive multiple of 64
+    _TAIL_FIELDS = (("ctx_any_length", C.c_int32),)
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        C.resize(self, _ATTN_CTX_DESC_BYTES)       # (before anyone takes the address: resize may move the buffer)
+        C.memset(C.addressof(self) + C.sizeof(type(self)), 0, _ATTN_CTX_DESC_BYTES - C.sizeof(type(self)))
+
+    @property
+    def ctx_any_length(self) -> int:
+        return C.c_int32.from_address(C.addressof(self) + _ATTN_CTX_ANY_LENGTH_OFFSET).value
+
+    @ctx_any_length.setter
+    def ctx_any_length(self, value: int) -> None:
+        C.c_int32.from_address(C.addressof(self) + _ATTN_CTX_ANY_LENGTH_OFFSET).value = int(value)
+
+
+def _tail_layout(cls):
+    """offsets of ``cls._TAIL_FIELDS`` behind ``cls._fields_`` and the C struct's size, by C's rules (natural alignment, the
+    struct padded to its strictest member's)"""
+    # (sizeof(cls) is padded already: the first tail field starts where the last named field ends)
+    last = getattr(cls, cls._fields_[-1][0])
+    off, offsets = last.offset + last.size, []
+    for _, t in cls._TAIL_FIELDS:
+        a = C.alignment(t)
+        off = (off + a - 1) // a * a
+        offsets.append(off)
+        off += C.sizeof(t)
+    a = C.alignment(cls)
+    return offsets, (off + a - 1) // a * a
+
+
+(_ATTN_CTX_ANY_LENGTH_OFFSET,), _ATTN_CTX_DESC_BYTES = _tail_layout(AttnCtxDesc)
 
 
 class HeadsDesc(C.Structure):

@@ -1369,6 +1369,9 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
   const int tile = pe[0], k0 = pe[1], k1 = pe[2];
   const int* te = plan_tiles(p) + (long)tile * TILE_INTS;
   const bool own = te[0] != 0;
+  // own parts mask behind the row's position and the part's end; a context piece only when its end is no tile boundary (the
+  // last piece of a context of any length, ctx_any_length) - workgroup-uniform, false for every whole-tile piece
+  const bool masked = own || (k1 % KB) != 0;
   const int key_row0 = te[1], n_rows = te[5];
   const int QS = TR / p.G;
 
@@ -1461,8 +1464,8 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
     for (int q = 0; q < 16; q += 2) do_pair(S, q, -mn, psum, pw[q >> 1]);
   };
 
-  // staging: chunk i of this thread = slot i * 256 + tid -> (row, 16-byte chunk); rows past k1 (own parts only: a context
-  // piece is whole tiles) re-read the last key and are masked
+  // staging: chunk i of this thread = slot i * 256 + tid -> (row, 16-byte chunk); rows past k1 (own parts, and the last
+  // piece of a context whose length is no multiple of 64) re-read the last key and are masked: no row behind k1 is touched
   u32x4 kreg[NL], vreg[NL];
   auto load_tile = [&](int kt) __attribute__((always_inline)) {
 #pragma unroll
@@ -1501,7 +1504,7 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
       for (int q = 0; q < 16; ++q) S[q] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < F; ++ks) S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], S, 0, 0, 0);
-      if (own) {
+      if (masked) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int key = kb + (q & 3) + 8 * (q >> 2) + 4 * hi;
@@ -1597,9 +1600,11 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
   const int QS = TR / G;
   MJV_REQUIRE(d->cu_seqlens[0] == 0 && (!d->cu_seqlens_q || d->cu_seqlens_q[0] == 0), "attention_ctx: cu_seqlens / cu_seqlens_q start at 0");
   MJV_REQUIRE(d->cu_context[0] >= 0, "attention_ctx: cu_context[0] < 0");
+  MJV_REQUIRE(d->ctx_any_length == 0 || d->ctx_any_length == 1, "attention_ctx: ctx_any_length %d not in {0, 1}", d->ctx_any_length);
   for (int c = 0; c < d->n_contexts; ++c) {
     const long len = (long)d->cu_context[c + 1] - d->cu_context[c];
-    MJV_REQUIRE(len > 0 && len % KB == 0, "attention_ctx: context %d has %ld keys - a positive multiple of %d is required", c, len, KB);
+    if (d->ctx_any_length) MJV_REQUIRE(len > 0, "attention_ctx: context %d has %ld keys - a positive length is required", c, len);
+    else MJV_REQUIRE(len > 0 && len % KB == 0, "attention_ctx: context %d has %ld keys - a positive multiple of %d is required", c, len, KB);
   }
   long total_q = 0;
   for (int s = 0; s < d->n_seqs; ++s) {
@@ -1628,8 +1633,9 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
   for (int c = 0; c < d->n_contexts; ++c) {
     if (!ctx_q[c]) continue;
     const long tiles = (ctx_q[c] + QS - 1) / QS;
-    const int kt = (d->cu_context[c + 1] - d->cu_context[c]) / KB;
-    // where a context is cut depends on ITS tiles and length alone; pieces of at least two key tiles
+    const int kt = (d->cu_context[c + 1] - d->cu_context[c] + KB - 1) / KB;   // key tiles; the last may be ragged (ctx_any_length)
+    // where a context is cut depends on ITS tiles and length alone; pieces of at least two key tiles, whole tiles except the
+    // context's last piece, which ends at the context's length
     long want = (TARGET_WG + tiles * n_kv - 1) / (tiles * n_kv);
     want = std::max(1l, std::min({want, (long)MAX_SPLIT, (long)std::max(1, kt / 2)}));
     const int chunk_t = (int)((kt + want - 1) / want);

@@ -147,28 +147,61 @@ def score_pair_batch(model, config, tokenizer, examples: Sequence[dict], generat
     return model.last_packed34.view(len(examples), 2, -1)
 
 
+def shared_prefix_len(rows, pad_id, gating_pattern=None) -> int:
+    """The longest context the full prompts ``rows`` of ONE video can share (``model.encode_video(..., context_len=...)``): the
+    length of their common prefix, capped so that every row keeps its reward row r and its gating row g outside the context -
+    min over rows of min(r, g), r and g as ``model.score_captions`` finds them (the last token before the first ``pad_id``;
+    the last occurrence of the gating pattern).  ``rows``: 1-D id sequences ([N] or [1, N] tensors / arrays), padded or not.
+    Two identical prompts share everything; the cap is what keeps their selected rows among the own rows."""
+    from .modeling import find_token_for_gating
+    rows = [np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r).reshape(-1) for r in rows]
+    if not rows:
+        raise ValueError("shared_prefix_len needs at least one prompt")
+    n = min(r.shape[0] for r in rows)
+    common = n
+    for r in rows[1:]:
+        differ = np.flatnonzero(r[:n] != rows[0][:n])
+        if differ.size:
+            common = min(common, int(differ[0]))
+    cap = n
+    for r in rows:
+        N = r.shape[0]
+        last = N - 1 if pad_id is None else (int(np.argmax(r == pad_id)) - 1) % N
+        cap = min(cap, last, find_token_for_gating(r, gating_pattern))
+    k = min(common, cap)
+    if k < 1:
+        raise ValueError("shared_prefix_len: the prompts share no token that every row can leave to a context")
+    return k
+
+
 @torch.no_grad()
-def score_video_captions(model, config, tokenizer, pixels: torch.Tensor, captions: Sequence[str], generation_config: dict) -> torch.Tensor:
+def score_video_captions(model, config, tokenizer, pixels: torch.Tensor, captions: Sequence[str], generation_config: dict,
+                         context: str = "video") -> torch.Tensor:
     """ONE video ([F, 3, S, S]) under M captions: the video goes through the vision tower and the context part of the
     language tower once (``model.encode_video``), every caption as its own rows only (``model.score_captions``).
     Returns ``[M, 1 + n_aspects + n_objectives]`` fp32 - the rows ``model.forward`` gives for the M full prompts, up to fp32
-    summation order."""
-    return score_caption_matrix(model, config, tokenizer, [pixels], captions, generation_config)[0]
+    summation order.  ``context``: as in ``score_caption_matrix``."""
+    return score_caption_matrix(model, config, tokenizer, [pixels], captions, generation_config, context=context)[0]
 
 
 @torch.no_grad()
 def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor], captions: Sequence[str], generation_config: dict,
-                         max_rows: int = 64, videos_per_call: int = 1) -> torch.Tensor:
+                         max_rows: int = 64, videos_per_call: int = 1, context: str = "video") -> torch.Tensor:
     """V videos x M captions (caption-vs-distractor matrices, perturbed captions, re-caption choice): every video is encoded
     once, the V * M caption rows go through ``model.score_captions`` in as few calls as ``max_rows`` rows per call allow.
     ``videos_per_call`` > 1: the videos go through ``model.encode_videos`` in blocks of that many (one vision-tower and one
     context pass per block), a block's rows are scored and its contexts dropped before the next block is encoded - the contexts
-    alive at any time are one block's, whatever V is.  Returns ``[V, M, 1 + n_aspects + n_objectives]`` fp32."""
+    alive at any time are one block's, whatever V is.  ``context``: "video" - a context ends at the video tokens, cut down to a
+    multiple of 64 (``encode_video``'s default); "shared" - it holds the whole prefix the video's M prompts share
+    (``shared_prefix_len``: the rest of the video, the frame labels, any instruction before the caption), so those rows are not
+    recomputed per caption.  Returns ``[V, M, 1 + n_aspects + n_objectives]`` fp32."""
     _lib.assert_product_library()
     if max_rows < 1:
         raise ValueError("max_rows must be positive")
     if videos_per_call < 1:
         raise ValueError("videos_per_call must be positive")
+    if context not in ("video", "shared"):
+        raise ValueError(f"context {context!r} not in ('video', 'shared')")
     dev = model.model.device
     pad_id = model.config.pad_token_id
     if pad_id is None:
@@ -179,6 +212,11 @@ def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor
 
     def prompts_of(pv):
         return [prepare_chat_input(config, tokenizer, pv, video_prefix(pv.shape[0]) + c, generation_config, device="cpu")[0] for c in captions]
+
+    def context_len_of(rows):
+        if context == "video":
+            return None
+        return shared_prefix_len(rows, pad_id, getattr(model.config, "gating_token_pattern", None))
 
     def score_rows(ids, contexts, out):
         """rows r = video-major over ``contexts``; appends the packed rows of every call to ``out``"""
@@ -198,13 +236,14 @@ def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor
             pv = pv.to(torch.bfloat16)
             rows = prompts_of(pv)
             ids.extend(rows)
-            contexts.append(model.encode_video(pv.to(dev), rows[0]))
+            contexts.append(model.encode_video(pv.to(dev), rows[0], context_len=context_len_of(rows)))
         score_rows(ids, contexts, out)
     else:
         for b0 in range(0, V, videos_per_call):
             block = [pv.to(torch.bfloat16) for pv in videos[b0:b0 + videos_per_call]]
             rows = [prompts_of(pv) for pv in block]
-            contexts = model.encode_videos([pv.to(dev) for pv in block], [r[0] for r in rows])
+            contexts = model.encode_videos([pv.to(dev) for pv in block], [r[0] for r in rows],
+                                           context_len=None if context == "video" else [context_len_of(r) for r in rows])
             score_rows([r for per in rows for r in per], contexts, out)
             del contexts
     return torch.cat(out).view(V, M, -1)

@@ -1215,8 +1215,10 @@ class InternVLChatRewardModeling(nn.Module):
         rows gathered into one buffer per layer."""
         H, KV, G, hd, scale, mode = self._llm_geom()
         cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
-        plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev)
-        plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"]) if trim else None
+        ragged = any(c.P % 64 for c in ctxs)   # a context that ends inside a key tile (encode_video's ``context_len``)
+        plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, any_length=ragged)
+        plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"],
+                                    any_length=ragged) if trim else None
         ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
                        dtype=torch.uint8).view(-1)
         P_all, C, L = int(cu_ctx[-1]), len(ctxs), len(ctxs[0].k)
@@ -1646,17 +1648,21 @@ class InternVLChatRewardModeling(nn.Module):
 
     @torch.no_grad()
     def encode_video(self, pixel_values: torch.Tensor, input_ids: torch.Tensor,
-                     attention_mask: Optional[torch.Tensor] = None) -> VideoContext:
+                     attention_mask: Optional[torch.Tensor] = None, context_len: Optional[int] = None) -> VideoContext:
         """The part of a scoring forward that does not depend on the caption, once per video: the vision tower on
         ``pixel_values`` [tiles, 3, S, S] (bf16), then the language tower over the first ``P`` tokens of ``input_ids`` ALONE
         (one full prompt of that video, [N] or [1, N]; what follows the video tokens is ignored), keeping every layer's
         rotated keys and its values compact.  ``P`` = the column after the last <IMG_CONTEXT>, cut down to a multiple of 64
         (the attention kernels' key-tile rule): 2 112 at 8 x 256 image tokens with the synthetic prompt, 576 @224^2.  The
         projected embeddings of image tokens behind ``P`` (7 in that example) stay in the context and are re-spliced per
-        caption.  207.6 MB per video for MJ-VIDEO-2B at P = 2 112 (``VideoContext.nbytes``)."""
+        caption.  207.6 MB per video for MJ-VIDEO-2B at P = 2 112 (``VideoContext.nbytes``).
+        ``context_len`` = K (an int, 1 <= K <= N - 1): the context is the first K tokens of the prompt instead, wherever K
+        falls - behind the video (the whole prefix the captions of this video share: ``harness.shared_prefix_len``), exactly at
+        its end (no image token left over) or inside the image run.  Such a context is scored by ``caption_attention`` "shared"
+        only unless K is a multiple of 64."""
         dev = self.model.device
         self._caption_guard(dev)
-        a = self._analyse_video(pixel_values, input_ids, attention_mask)
+        a = self._analyse_video(pixel_values, input_ids, attention_mask, context_len=context_len)
         ids, N, P, cols, n_img, n_in = a["ids"], a["N"], a["P"], a["cols"], a["n_img"], a["n_in"]
         d = self._prepare(dev)
         ctx_id = self.model.img_context_token_id
@@ -1684,11 +1690,11 @@ class InternVLChatRewardModeling(nn.Module):
             stream = torch.cuda.current_stream(dev).cuda_stream
         return VideoContext(ids, P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
 
-    def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = ""):
+    def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = "", context_len: Optional[int] = None):
         """The checks of ``encode_video`` / ``encode_videos`` on ONE video and its prompt ([N] or [1, N]; nothing is repaired), and
         what the context pass needs of them: the first P ids, P (the column after the last <IMG_CONTEXT>, cut down to a multiple
-        of 64), the <IMG_CONTEXT> columns and how many lie inside P.  Host code: reads the tensors' shapes / dtypes and the ids.
-        ``who``: what the messages of a many-video call start with."""
+        of 64; or ``context_len``, any 1 <= K <= N - 1), the <IMG_CONTEXT> columns and how many lie inside P.  Host code: reads
+        the tensors' shapes / dtypes and the ids.  ``who``: what the messages of a many-video call start with."""
         if pixel_values.dim() != 4:
             raise ValueError(f"{who}wrong pixel_values size: {tuple(pixel_values.shape)}")
         if pixel_values.dtype != BF16:
@@ -1705,9 +1711,15 @@ class InternVLChatRewardModeling(nn.Module):
         if cols.size != n_img or n_img == 0:
             raise ValueError(f"{who}{cols.size} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {tiles} tiles x "
                              f"{self.model.num_image_token} image tokens")
-        P = ((int(cols[-1]) + 1) // 64) * 64
-        if P <= 0:
-            raise ValueError(f"{who}the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
+        if context_len is None:
+            P = ((int(cols[-1]) + 1) // 64) * 64
+            if P <= 0:
+                raise ValueError(f"{who}the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
+        else:
+            if isinstance(context_len, bool) or not isinstance(context_len, (int, np.integer)) or not 1 <= context_len <= N - 1:
+                raise ValueError(f"{who}context_len must be None or an int in [1, {N - 1}] (the prompt has {N} tokens), "
+                                 f"got {context_len!r}")
+            P = int(context_len)
         if attention_mask is not None:
             am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
             if am.shape[0] != N:
@@ -1720,7 +1732,7 @@ class InternVLChatRewardModeling(nn.Module):
             raise IndexError(f"{who}token id out of range [0, {vocab})")
         return dict(ids=ids[:P].copy(), N=N, P=P, tiles=tiles, n_img=n_img, n_in=int((cols < P).sum()), cols=cols)
 
-    def _analyse_videos(self, pixel_values, input_ids, attention_mask=None):
+    def _analyse_videos(self, pixel_values, input_ids, attention_mask=None, context_len=None):
         """``encode_videos``' checks - ``_analyse_video`` video by video, every message naming its video - and the packed layout
         of the context pass.  Host code, as ``_analyse_captions`` is."""
         if isinstance(pixel_values, torch.Tensor) or isinstance(input_ids, torch.Tensor):
@@ -1734,9 +1746,15 @@ class InternVLChatRewardModeling(nn.Module):
         if len(input_ids) != V or len(masks) != V:
             raise ValueError(f"encode_videos: {V} videos, {len(input_ids)} prompts" +
                              ("" if attention_mask is None else f", {len(masks)} attention masks"))
+        if context_len is None or isinstance(context_len, (int, float, np.number)):   # one rule for every video
+            lens = [context_len] * V
+        else:
+            lens = list(context_len)
+            if len(lens) != V:
+                raise ValueError(f"encode_videos: {V} videos, context_len of {len(lens)} entries (None, one int, or one per video)")
         vids = []
         for v, (px, ids_t, am_t) in enumerate(zip(pixel_values, input_ids, masks)):
-            vids.append(self._analyse_video(px, ids_t, am_t, who=f"video {v}: "))
+            vids.append(self._analyse_video(px, ids_t, am_t, who=f"video {v}: ", context_len=lens[v]))
             if tuple(px.shape[1:]) != tuple(pixel_values[0].shape[1:]):
                 raise ValueError(f"video {v}: tiles of {tuple(px.shape[1:])}, video 0 has {tuple(pixel_values[0].shape[1:])} "
                                  "(one vision-tower pass takes one tile size)")
@@ -1751,17 +1769,19 @@ class InternVLChatRewardModeling(nn.Module):
                     positions=np.concatenate([np.arange(x["P"]) for x in vids]).astype(np.int32), img_rows=img_rows)
 
     @torch.no_grad()
-    def encode_videos(self, pixel_values, input_ids, attention_mask=None) -> List[VideoContext]:
+    def encode_videos(self, pixel_values, input_ids, attention_mask=None, context_len=None) -> List[VideoContext]:
         """``encode_video`` for V videos in one pass: ``pixel_values`` / ``input_ids`` (/ ``attention_mask``) are sequences of what
         ``encode_video`` takes per video.  ONE vision-tower pass over all tiles, ONE language-tower pass over the sum of the
         videos' context rows, packed (every video a sequence of its own: positions from 0, causal within the video).  Every
         layer's rotated keys and compact values land in one buffer per layer for the whole call; the returned contexts are row
         ranges of those buffers (``VideoContext.clone()`` for an owning copy).  The rotary width is the longest prompt's, and
         every context carries the settings of that width.  A video's rows are what ``encode_video`` computes for it alone - bit
-        for bit when no GEMM slices K, up to fp32 re-association otherwise."""
+        for bit when no GEMM slices K, up to fp32 re-association otherwise.  ``context_len``: as in
+        ``encode_video`` - None, one int for all videos, or a sequence of one entry per video; a view then starts at whatever row
+        the lengths before it add up to (its 16-byte alignment is the leading dimension's)."""
         dev = self.model.device
         self._caption_guard(dev)
-        info = self._analyse_videos(pixel_values, input_ids, attention_mask)
+        info = self._analyse_videos(pixel_values, input_ids, attention_mask, context_len)
         d = self._prepare(dev)
         lc = self.config.llm_config
         hdim, total, n_tail = lc.hidden_size, info["total"], int(info["cu_tail"][-1])
@@ -1889,6 +1909,11 @@ class InternVLChatRewardModeling(nn.Module):
             raise ValueError(f"caption_context_rows {self.caption_context_rows!r} not in ('in-place', 'packed')")
         if input_ids.dim() != 2:
             raise ValueError(f"input_ids must be [captions, seq], got {tuple(input_ids.shape)}")
+        if self.caption_attention == "per-context":   # mjv_attention_bf16's prefix rule; the shared launch takes any length
+            for c, ctx in enumerate(ctxs):
+                if ctx.P % 64:
+                    raise ValueError(f"context {c} holds {ctx.P} tokens: caption_attention 'per-context' needs a context length "
+                                     "that is a multiple of 64 (prefix_len % 64 == 0); use 'shared' for a context of any length")
         d = self._prepare(dev)
         M, N = int(input_ids.shape[0]), int(input_ids.shape[1])
         if context_index is None:

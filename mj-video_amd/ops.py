@@ -267,8 +267,9 @@ class AttnCtxPlan:
     them, and the size of the fp32 partials.  Built once per batch, used by every layer's launch."""
 
     def __init__(self, cu_seqlens, context_index, cu_context, n_heads: int, kv_group: int, head_dim: int, device,
-                 cu_seqlens_q=None):
+                 cu_seqlens_q=None, any_length: bool = False):
         import numpy as np
+        self.any_length = bool(any_length)   # contexts of any positive length (mjv_attn_ctx_desc.ctx_any_length); False: multiples of 64
         as_i32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32))  # noqa: E731
         self.cu, self.cu_q, self.index, self.cu_ctx = as_i32(cu_seqlens), as_i32(cu_seqlens_q), as_i32(context_index), as_i32(cu_context)
         if self.cu.ndim != 1 or self.cu.size < 2 or self.index.shape != (self.cu.size - 1,) or self.cu_ctx.ndim != 1 or self.cu_ctx.size < 2 \
@@ -293,6 +294,7 @@ class AttnCtxPlan:
         d.cu_seqlens_q = None if self.cu_q is None else self.cu_q.ctypes.data
         d.n_seqs, d.n_contexts = self.cu.size - 1, self.cu_ctx.size - 1
         d.n_heads, d.kv_group, d.head_dim, d.causal = self.n_heads, self.kv_group, self.head_dim, 1
+        d.ctx_any_length = int(self.any_length)
         return d
 
 

@@ -1,6 +1,7 @@
 """Many captions per video: ``encode_video`` + ``score_captions`` against ``forward`` on the same full prompts.
 
     python tools/caption_bench.py [--m 1,2,4,8,16,64] [--reps 5] [--out FILE.json] [--matrix 8x8] [--size 448] [--frames 8]
+                                  [--context video,shared] [--no-forward]
 
 MJ-VIDEO-2B dims, random-init weights generated on the device (bench.py's), 8 frames @448^2, captions of 24 - 96 tokens.
 (``--m ""``: the matrix part alone.)  Per M: ms of ``encode_video``; ms of ``score_captions`` with caption_attention "shared" and "per-context" (alternated rep by rep
@@ -9,7 +10,11 @@ the baseline); captions/s.  Every shape is warmed first; a timed region is brack
 synchronise.  Then the library profiler's per-tag table of one caption pass (attention share, small-GEMM share) and V x M
 through ``harness.score_caption_matrix`` - one video per ``encode_video`` call against all V through ONE ``encode_videos`` call,
 and one ``score_captions`` call over the V contexts with ``caption_context_rows`` "packed" against "in-place" - the arms of
-every pair alternated rep by rep.  One JSON document on stdout (and in --out).
+every pair alternated rep by rep.  ``--context video,shared`` adds the pair of context rules: a context that ends at the video
+tokens cut down to a multiple of 64 (``encode_video``'s default) against one that holds the whole prefix the M prompts share
+(``harness.shared_prefix_len``) - per M the context tokens, caption rows, ``score_captions`` ms and encode ms of both arms, and
+the V x M matrix under ``context="video"`` / ``"shared"``, alternated rep by rep like every other pair.  ``--no-forward`` leaves
+the ``forward`` baseline out.  One JSON document on stdout (and in --out).
 """
 import argparse
 import json
@@ -68,6 +73,18 @@ def timed(fn, reps):
     return dict(median_ms=statistics.median(ms), min_ms=min(ms), reps=reps)
 
 
+def alternated(arms, reps):
+    """{name: fn} -> {name: median / min ms}: every arm warmed once, then the arms in turn, ``reps`` rounds"""
+    for fn in arms.values():
+        fn()
+    ms = {name: [] for name in arms}
+    for _ in range(reps):
+        for name, fn in arms.items():
+            ms[name].append(timed(fn, 1)["median_ms"])
+    return {name: dict(median_ms=statistics.median(v), min_ms=min(v), reps=len(v), all_ms=[round(x, 3) for x in v])
+            for name, v in ms.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", default="1,2,4,8,16,64")
@@ -76,7 +93,12 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--matrix", default="8x8")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--context", default="video", help="video, or video,shared: the pair of context rules, alternated")
+    ap.add_argument("--no-forward", action="store_true", help="leave the forward baseline out")
     args = ap.parse_args()
+    context_arms = [a for a in args.context.split(",") if a]
+    if not context_arms or any(a not in ("video", "shared") for a in context_arms):
+        ap.error("--context takes video, shared or both")
     dev = torch.device("cuda:0")
     cfg = C.InternVLChatRewardModelingConfig(**C.mjvideo_2b_config_dict(args.size), **C.mjvideo_head_kwargs())
     model = InternVLChatRewardModeling.from_config(cfg, dtype=torch.bfloat16, device=dev)
@@ -105,7 +127,8 @@ def main():
         for mode in ("shared", "per-context"):       # warm every shape
             model.caption_attention = mode
             model.score_captions(ctx, ids, mask)
-        forward_all(ids, mask, M)
+        if not args.no_forward:
+            forward_all(ids, mask, M)
         torch.cuda.synchronize()
         row = dict(M=M, context_tokens=ctx.P, context_bytes=ctx.nbytes, caption_rows=int(mask.sum().item()) - M * ctx.P)
         row["encode_video"] = timed(lambda: model.encode_video(px, prompts[0]), args.reps)
@@ -117,10 +140,22 @@ def main():
         for mode, ms in res.items():
             row[f"score_captions[{mode}]"] = dict(median_ms=statistics.median(ms), min_ms=min(ms), reps=len(ms))
         model.caption_attention = "shared"
-        row["forward"] = timed(lambda: forward_all(ids, mask, M), max(2, args.reps // 2))
         cap = row["score_captions[shared]"]["median_ms"]
-        row["captions_per_s"] = dict(encode_plus_shared=1e3 * M / (row["encode_video"]["median_ms"] + cap), shared_warm_context=1e3 * M / cap,
-                                     forward=1e3 * M / row["forward"]["median_ms"])
+        row["captions_per_s"] = dict(encode_plus_shared=1e3 * M / (row["encode_video"]["median_ms"] + cap), shared_warm_context=1e3 * M / cap)
+        if not args.no_forward:
+            row["forward"] = timed(lambda: forward_all(ids, mask, M), max(2, args.reps // 2))
+            row["captions_per_s"]["forward"] = 1e3 * M / row["forward"]["median_ms"]
+        if len(context_arms) > 1:   # the two context rules on the same prompts (caption_attention "shared")
+            klen = {"video": None, "shared": harness.shared_prefix_len(prompts, synth.PAD_ID)}
+            ctxs = {a: model.encode_video(px, prompts[0], context_len=klen[a]) for a in context_arms}
+            enc = alternated({a: (lambda a=a: model.encode_video(px, prompts[0], context_len=klen[a])) for a in context_arms}, args.reps)
+            sc = alternated({a: (lambda a=a: model.score_captions(ctxs[a], ids, mask)) for a in context_arms}, args.reps)
+            row["context_arms"] = {a: dict(context_tokens=ctxs[a].P, caption_rows=int(mask.sum().item()) - M * ctxs[a].P,
+                                           encode_video=enc[a], score_captions=sc[a]) for a in context_arms}
+            print(f"M={M}: " + "; ".join(f"context {a}: {v['context_tokens']} tokens, {v['caption_rows']} caption rows, score_captions "
+                                         f"{v['score_captions']['median_ms']:.2f} ms, encode {v['encode_video']['median_ms']:.2f} ms"
+                                         for a, v in row["context_arms"].items()), file=sys.stderr, flush=True)
+            del ctxs
         # the library profiler's per-tag table of ONE caption pass
         ops.prof_enable(True)
         ops.prof_reset()
@@ -137,7 +172,8 @@ def main():
                                           sum_of_kernels_ms=round(total, 4))
         doc["rows"].append(row)
         print(f"M={M}: encode {row['encode_video']['median_ms']:.2f} ms, score_captions shared {cap:.2f} / per-context "
-              f"{row['score_captions[per-context]']['median_ms']:.2f} ms, forward {row['forward']['median_ms']:.2f} ms", file=sys.stderr, flush=True)
+              f"{row['score_captions[per-context]']['median_ms']:.2f} ms" +
+              ("" if args.no_forward else f", forward {row['forward']['median_ms']:.2f} ms"), file=sys.stderr, flush=True)
         del ctx
 
     if args.matrix:
@@ -148,22 +184,11 @@ def main():
         captions = ["".join(chr(97 + (i * 7 + j) % 26) for j in range(24 + (i * 37) % 73)) for i in range(M)]
         reps = max(2, args.reps)
 
-        def alternated(arms):
-            """{name: fn} -> {name: median / min ms}: every arm warmed once, then the arms in turn, ``reps`` rounds"""
-            for fn in arms.values():
-                fn()
-            ms = {name: [] for name in arms}
-            for _ in range(reps):
-                for name, fn in arms.items():
-                    ms[name].append(timed(fn, 1)["median_ms"])
-            return {name: dict(median_ms=statistics.median(v), min_ms=min(v), reps=len(v), all_ms=[round(x, 3) for x in v])
-                    for name, v in ms.items()}
-
         def matrix(per_call):
             return lambda: harness.score_caption_matrix(model, cfg, tok, videos, captions, {}, max_rows=64, videos_per_call=per_call)
 
         doc["matrix"] = dict(V=V, M=M, note="host tokenisation of the V x M prompts included; ceil(V M / 64) score_captions calls",
-                             score_caption_matrix=alternated({"videos_per_call=1": matrix(1), f"videos_per_call={V}": matrix(V)}))
+                             score_caption_matrix=alternated({"videos_per_call=1": matrix(1), f"videos_per_call={V}": matrix(V)}, reps))
         # the same call's parts on their own: the V encodes (one call per video / one call for all), and ONE score_captions
         # call of V * M rows over V contexts: contexts read in place / gathered into one packed buffer per layer / one launch per
         # context
@@ -173,7 +198,7 @@ def main():
         index = torch.tensor([v for v in range(V) for _ in range(M)])
         firsts = [rows[v][0] for v in range(V)]
         doc["matrix"]["encode"] = alternated({"encode_video_x_V": lambda: [model.encode_video(pv, firsts[v]) for v, pv in enumerate(videos)],
-                                              "encode_videos": lambda: model.encode_videos(videos, firsts)})
+                                              "encode_videos": lambda: model.encode_videos(videos, firsts)}, reps)
 
         def score(ctxs, rows_mode, attention):
             def run():
@@ -187,8 +212,23 @@ def main():
         doc["matrix"]["score_captions"] = alternated({"shared,packed": score(owned, "packed", "shared"),
                                                       "shared,in-place": score(owned, "in-place", "shared"),
                                                       "shared,in-place,views": score(views, "in-place", "shared"),
-                                                      "per-context": score(owned, "in-place", "per-context")})
+                                                      "per-context": score(owned, "in-place", "per-context")}, reps)
         model.caption_context_rows, model.caption_attention = "in-place", "shared"
+        if len(context_arms) > 1:
+            # the whole harness call under both context rules, and its parts: the V encodes and ONE score_captions call
+            def matrix_ctx(a):
+                return lambda: harness.score_caption_matrix(model, cfg, tok, videos, captions, {}, max_rows=64, context=a)
+
+            klen = {"video": [None] * V, "shared": [harness.shared_prefix_len(rows[v], model.config.pad_token_id) for v in range(V)]}
+            ctxs = {a: [model.encode_video(pv, firsts[v], context_len=klen[a][v]) for v, pv in enumerate(videos)] for a in context_arms}
+            n_rows = int(mask.sum().item())
+            doc["matrix"]["context_arms"] = dict(
+                context_tokens={a: [c.P for c in ctxs[a]] for a in context_arms},
+                caption_rows={a: n_rows - M * sum(c.P for c in ctxs[a]) for a in context_arms},
+                score_caption_matrix=alternated({a: matrix_ctx(a) for a in context_arms}, reps),
+                encode_video_x_V=alternated({a: (lambda a=a: [model.encode_video(pv, firsts[v], context_len=klen[a][v])
+                                                              for v, pv in enumerate(videos)]) for a in context_arms}, reps),
+                score_captions=alternated({a: score(ctxs[a], "in-place", "shared") for a in context_arms}, reps))
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:
