@@ -38,6 +38,8 @@
  * ABI 7, additive (MJV_ABI_VERSION stays 7, no new symbol): one field at the END of mjv_attn_ctx_desc, ctx_any_length - 0 = as
  * before (a context is a positive multiple of 64 keys), 1 = a context may end at any key, so a caller can cache the whole
  * prefix that the captions of a video share.
+ * ABI 7, additive (MJV_ABI_VERSION stays 7): mjv_gemm_plan - the launches mjv_gemm_bf16 makes for a descriptor, readable without
+ * a GPU and for any number of compute units.
  */
 #ifndef MJV_H_
 #define MJV_H_
@@ -166,6 +168,20 @@ typedef struct mjv_gemm_desc {
 int64_t mjv_gemm_workspace_bytes(void);
 
 int mjv_gemm_bf16(const mjv_gemm_desc* d, void* stream);
+
+/* ABI 7, additive.  Writes the launches mjv_gemm_bf16 would make for *d (bf16 or MXFP8 operands; the descriptor is checked as
+ * there, nothing it points to is read) on a device with `cus` compute units (cus <= 0: the current device).  Touches no device
+ * memory, launches nothing.  Returns the number of int32 written (or needed, when out == NULL), or a negative error code.
+ *   out[0 .. 3]          {n_launches (1 or 2), gm (group-M of the 256-tile order), nt_store (1 = streaming output stores), 0}
+ *   out[4 + 8 i .. + 7]  launch i, in stream order; the launches' rows partition [0, M), a first of two has rows % 256 == 0:
+ *     [0] family           64 = 64 x 32 skinny kernel, 128 = 128 x 128, 256 = 256 x 256 (bf16 and MXFP8), 2 = tile code 2
+ *     [1] epilogue         the one this launch runs (MJV_EPI_BIAS where rows of a ROPE_QKV problem take the fallback, see [7])
+ *     [2] row0, [3] rows
+ *     [4] split            K slices per tile through the workspace (1 = none; > 1: the slice kernel and its finish kernel)
+ *     [5] grid             workgroups of the main kernel
+ *     [6] persistent       1 = the persistent 256-tile kernel (grid == cus workgroups walk the tiles)
+ *     [7] rope_split_after 1 = the launch writes the plain Linear and mjv_rope_split_bf16 on its rows follows */
+int64_t mjv_gemm_plan(const mjv_gemm_desc* d, int32_t cus, int32_t* out, int64_t out_ints);
 
 /* ---------------------------------------------------------------------------------------------
  * Flash-style attention over packed variable-length sequences (no N x N scores in HBM).

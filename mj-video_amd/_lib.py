@@ -127,6 +127,7 @@ SYMBOLS = {
     "mjv_arch": (C.c_char_p, []),
     "mjv_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), _VP]),
     "mjv_gemm_workspace_bytes": (C.c_int64, []),
+    "mjv_gemm_plan": (C.c_int64, [C.POINTER(GemmDesc), _I32, _VP, _I64]),
     "mjv_attention_bf16": (C.c_int, [C.POINTER(AttnDesc), _VP]),
     "mjv_attention_ctx_plan": (C.c_int64, [C.POINTER(AttnCtxDesc), _VP, _I64]),
     "mjv_attention_ctx_workspace_bytes": (C.c_int64, [C.POINTER(AttnCtxDesc)]),

@@ -27,8 +27,11 @@
 // and the epilogue moves 8 bytes per lane per access.
 //
 // Epilogues reproduce the reference's bf16 op boundaries (one rounding per torch op).
+//
+// Launch policy - which of these kernels a descriptor gets, peeled tail rows, K slices, the persistent form, profiler tags -
+// lives in gemm_plan.h (host-only, exported as mjv_gemm_plan); the host code at the end of this file checks, plans, executes.
 #include "gemm_common.h"
-#include <atomic>
+#include "gemm_plan.h"
 
 namespace {
 
@@ -1407,12 +1410,6 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(GemmArgs p) {
 
 }  // namespace t256
 
-thread_local int g_num_cus = 256;   // CUs of the device of the call in flight (mjv_device_cus), set in mjv_gemm_bf16
-
-// Measurement knobs.  The product library (default build) has none: the values below are constants, the kernel variants that
-// skip work (wrong results by construction) are not compiled, and what a caller may choose - the tile kernel, for parity
-// tests - travels in the call's descriptor (mjv_gemm_desc.tile).  -DMJV_BENCH (make bench -> libmjv_hip_bench.so, loaded by
-// tools/gemm_bench.py and friends) turns them into process-wide settings behind mjv_bench_gemm_set().
 // ============================================================================================ 128 x 256, two workgroups per CU
 // Round 6: the structural alternative to "one 256 x 256 workgroup owns the CU" for the SHORT-K Linears of the
 // vision tower (qkv, fc1, proj: K = 1024 = 16 K-tiles of the 256^2 kernel, where the un-overlapped epilogue is a quarter to a
@@ -1602,175 +1599,155 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs p) {
 }
 }  // namespace t2
 
-struct GemmTune {
-  int gm = 0;               // group-M of the 256-tile order: 0 = by shape (pick_gm)
-  int skinny_max_m = 128;   // problems with at most this many rows run on the 64 x 32 kernel
-  int split_max = 8;        // cap on the K slices per tile
-  int split_k = 1;          // split-K for under-filled 128-tile launches when the caller gives a workspace
-  int variant = 0;          // 256-tile kernel variant (3: no epilogue, 4: no global stores, 6: s_memtime stamps)
-  int split256_min_kt = 8;  // fewest K-tiles per slice of the K-sliced 256-tile launches
-  int split256 = 1;         // under-filled problems with deep K run as K slices of 256 x 256 tiles
-  int split256_min_nk = 64; // ... deep = at least this many 64-wide K-tiles (bench: 4400 + n)
-  int nt = -1;              // streaming output stores: -1 = by shape, 0 / 1 = never / always
-  void* stamp_buffer = nullptr;
-};
 #ifdef MJV_BENCH
-GemmTune g_tune;
-#define MJV_TUNE(f) (g_tune.f)
+GemmTune g_tune;             // process-wide, behind mjv_bench_gemm_set()
 #else
-constexpr GemmTune g_tune_const{};
-#define MJV_TUNE(f) (g_tune_const.f)
+constexpr GemmTune g_tune{}; // the product library's constants (gemm_plan.h)
 #endif
 
+// Executes one planned launch (gemm_plan.h decides; nothing is decided here).  The `if constexpr` guards keep kernels that no
+// plan launches from being instantiated.
 template <int EPI>
-int launch(GemmArgs a, hipStream_t s, bool big, bool skinny = false) {
-  if (skinny) {
-    // (a 64 x 128 tile of the same kernel for the ~1100-row tails of the language tower measured 8 % slower than the
-    // 128 x 128 kernel with split-K: 3.67 vs 3.30 ms per step on the residual GEMMs; only NJ = 2 is instantiated)
-    a.tiles_m = (a.M + t64::BM - 1) / t64::BM;
-    a.tiles_n = (a.N + 31) / 32;
-    hipLaunchKernelGGL((t64::gemm_skinny_kernel<EPI, 2>), dim3(a.tiles_m * a.tiles_n), dim3(256), t64::Cfg<2>::LDS_BYTES, s, a);
+int launch(GemmArgs a, const GemmLaunch& L, hipStream_t s) {
+  a.tiles_m = L.tiles_m, a.tiles_n = L.tiles_n;
+  if (L.family == 64) {   // (only NJ = 2 is instantiated)
+    hipLaunchKernelGGL((t64::gemm_skinny_kernel<EPI, 2>), dim3(L.grid), dim3(256), t64::Cfg<2>::LDS_BYTES, s, a);
     return mjv_check_launch("gemm_bf16");
   }
   constexpr int LDS1 = EPI == MJV_EPI_BIAS_GELU ? t256::LDS_BYTES_G : t256::LDS_BYTES;   // (the GELU kernels' map uses all 160 KiB)
-  // the dynamic-LDS limit is a per-device function attribute: set it once on every device this instantiation runs on
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)t128::gemm128_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, t128::LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)t128::gemm128_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, t128::LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
+  constexpr int LDSF = EPI == MJV_EPI_BIAS_GELU ? t256::LDS_BYTES_G : t256::LDS_BYTES_FUSE;
+  constexpr int WANT = gemm_fuse_of(EPI);   // the norm the 256-tile kernels of this epilogue can have folded in
+  static MjvOncePerDevice once;
+  once([] {
+    MJV_MAX_LDS((t128::gemm128_kernel<EPI, false>), t128::LDS_BYTES);
+    MJV_MAX_LDS((t128::gemm128_kernel<EPI, true>), t128::LDS_BYTES);
+    MJV_MAX_LDS((t256::gemm256_kernel<EPI, 0>), LDS1);
 #ifdef MJV_BENCH
-    (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-    (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-    (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
+    MJV_MAX_LDS((t256::gemm256_kernel<EPI, 3>), LDS1);
+    MJV_MAX_LDS((t256::gemm256_kernel<EPI, 4>), LDS1);
+    MJV_MAX_LDS((t256::gemm256_kernel<EPI, 6>), LDS1);
 #endif
-    (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<MJV_EPI_BIAS, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES);
+    MJV_MAX_LDS((t256::gemm256_kernel<MJV_EPI_BIAS, 7>), t256::LDS_BYTES);
     // (the persistent form is instantiated for the three epilogues that launch it - ADVICE r3: the LayerScale / GELU
     // instantiations were compiled, spilled 13 / 62 registers and were never launched or tested)
     if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_RELU || EPI == MJV_EPI_SILU_MUL)
-      (void)hipFuncSetAttribute((const void*)t256::gemm256p_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES);
-    // a norm folded into the GEMM: LayerNorm into the ViT's qkv / fc1 (bias epilogues), RMSNorm into wqkv / w1|w3
-    if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_GELU)
-      (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                EPI == MJV_EPI_BIAS_GELU ? t256::LDS_BYTES_G : t256::LDS_BYTES_FUSE);
-    if constexpr (EPI == MJV_EPI_SILU_MUL || EPI == MJV_EPI_ROPE_QKV)
-      (void)hipFuncSetAttribute((const void*)t256::gemm256_kernel<EPI, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES_FUSE);
-    if constexpr (EPI == MJV_EPI_BIAS)
-      (void)hipFuncSetAttribute((const void*)t256::gemm256p_kernel<EPI, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES_FUSE_P);
-    if constexpr (EPI == MJV_EPI_SILU_MUL)
-      (void)hipFuncSetAttribute((const void*)t256::gemm256p_kernel<EPI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES_FUSE_P);
-    attr_done.fetch_or(bit, std::memory_order_release);   // racing first calls both set the attributes: idempotent
-  }
-  const int fuse = a.row_scale ? (a.row_shift ? 2 : 1) : 0;
-  if (big && a.split <= 1 && fuse) {
-    // the 256 x 256 kernels instantiate the folded-norm epilogue where the model uses it; the small kernels and the K-sliced
-    // finish take every combination (store_frags)
-    a.tiles_m = (a.M + 255) / 256;
-    a.tiles_n = (a.N + 255) / 256;
-    const int tiles = a.tiles_m * a.tiles_n, nk = a.K / 64;
-    const bool persistent = tiles > g_num_cus && nk >= 4 && (nk & 1) == 0;
-    constexpr int WANT = (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_GELU) ? 2 : (EPI == MJV_EPI_SILU_MUL || EPI == MJV_EPI_ROPE_QKV) ? 1 : 0;
-    if constexpr (WANT != 0) {
-      if (fuse == WANT) {
-        if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_SILU_MUL) {
-          if (persistent) {
-            hipLaunchKernelGGL((t256::gemm256p_kernel<EPI, WANT>), dim3(g_num_cus), dim3(512), t256::LDS_BYTES_FUSE_P, s, a);
-            return mjv_check_launch("gemm_bf16");
-          }
-        }
-        hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 0, WANT>), dim3(tiles), dim3(512),
-                           EPI == MJV_EPI_BIAS_GELU ? t256::LDS_BYTES_G : t256::LDS_BYTES_FUSE, s, a);
-        return mjv_check_launch("gemm_bf16");
-      }
-    }
-    mjv_set_error("gemm: the 256-tile kernel has no instantiation for epilogue %d with %s folded in (bias / bias+GELU take a "
-                  "LayerNorm: row_scale + row_shift; SiLU-mul / RoPE-qkv an RMSNorm: row_scale only)", (int)EPI,
-                  fuse == 2 ? "row_scale + row_shift" : "row_scale");
-    return MJV_E_UNSUPPORTED;
-  }
-  if (big) {
-    a.tiles_m = (a.M + 255) / 256;
-    a.tiles_n = (a.N + 255) / 256;
-    if (a.split > 1) {
-      const int tiles = a.tiles_m * a.tiles_n;
-      hipLaunchKernelGGL((t256::gemm256_kernel<MJV_EPI_BIAS, 7>), dim3(tiles * a.split), dim3(512), t256::LDS_BYTES, s, a);
-      hipLaunchKernelGGL(t256::splitk_finish256_kernel<EPI>, dim3(tiles * 8), dim3(512), 0, s, a);
-    }
-#ifdef MJV_BENCH
-    else if (MJV_TUNE(variant) == 6) {
-      a.ws = (float*)MJV_TUNE(stamp_buffer);
-      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 6>), dim3(a.tiles_m * a.tiles_n), dim3(512), LDS1, s, a);
-    } else if (MJV_TUNE(variant) == 4)
-      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 4>), dim3(a.tiles_m * a.tiles_n), dim3(512), LDS1, s, a);
-    else if (MJV_TUNE(variant) == 3)
-      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 3>), dim3(a.tiles_m * a.tiles_n), dim3(512), LDS1, s, a);
-#endif
-    else {
-      // persistent form (one workgroup per CU walks the tiles, next tile's first K-tile prefetched under the epilogue) when the
-      // launch has more tiles than CUs and an even number (>= 4) of K-tiles; the rotary epilogue keeps the one-tile kernel
-      const int tiles = a.tiles_m * a.tiles_n, nk = a.K / 64;
-      // (measured per epilogue, tools/gemm_bench.py 1000 / 1009 in one process: +1.4 ... +2.1 % for the plain-bias and SiLU
-      // epilogues; the LayerScale / residual epilogue loses 6-24 % - its 64 residual registers on top of the persistent
-      // loop's state spill - and the GELU epilogue 29 % - half the table gathers in flight per vote - so those keep the
-      // one-tile kernel)
-      bool persistent = (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_RELU || EPI == MJV_EPI_SILU_MUL) && tiles > g_num_cus &&
-                        nk >= 4 && (nk & 1) == 0;
-#ifdef MJV_BENCH
-      if (MJV_TUNE(variant) == 9) persistent = false;   // A/B: the one-tile-per-workgroup kernel
-      a.ws = MJV_TUNE(variant) == 8 ? (float*)MJV_TUNE(stamp_buffer) : nullptr;   // 1008: main-loop clock stamps (persistent form)
-#endif
-      if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_RELU || EPI == MJV_EPI_SILU_MUL) {
-        if (persistent) {
-          hipLaunchKernelGGL((t256::gemm256p_kernel<EPI>), dim3(g_num_cus), dim3(512), t256::LDS_BYTES, s, a);
+      MJV_MAX_LDS((t256::gemm256p_kernel<EPI>), t256::LDS_BYTES);
+    if constexpr (WANT != 0) MJV_MAX_LDS((t256::gemm256_kernel<EPI, 0, WANT>), LDSF);
+    if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_SILU_MUL) MJV_MAX_LDS((t256::gemm256p_kernel<EPI, WANT>), t256::LDS_BYTES_FUSE_P);
+  });
+  if (L.family == 256 && L.fuse) {
+    if constexpr (WANT != 0) {   // (the plan holds L.fuse == WANT)
+      if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_SILU_MUL) {
+        if (L.persistent) {
+          hipLaunchKernelGGL((t256::gemm256p_kernel<EPI, WANT>), dim3(L.grid), dim3(512), t256::LDS_BYTES_FUSE_P, s, a);
           return mjv_check_launch("gemm_bf16");
         }
       }
-      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 0>), dim3(a.tiles_m * a.tiles_n), dim3(512), LDS1, s, a);
+      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 0, WANT>), dim3(L.grid), dim3(512), LDSF, s, a);
     }
+  } else if (L.family == 256) {
+    if (L.split > 1) {
+      hipLaunchKernelGGL((t256::gemm256_kernel<MJV_EPI_BIAS, 7>), dim3(L.grid), dim3(512), t256::LDS_BYTES, s, a);
+      hipLaunchKernelGGL(t256::splitk_finish256_kernel<EPI>, dim3(L.tiles_m * L.tiles_n * 8), dim3(512), 0, s, a);
+    }
+#ifdef MJV_BENCH
+    else if (g_tune.variant == 6) {
+      a.ws = (float*)g_tune.stamp_buffer;
+      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 6>), dim3(L.grid), dim3(512), LDS1, s, a);
+    } else if (g_tune.variant == 4)
+      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 4>), dim3(L.grid), dim3(512), LDS1, s, a);
+    else if (g_tune.variant == 3)
+      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 3>), dim3(L.grid), dim3(512), LDS1, s, a);
+#endif
+    else {
+#ifdef MJV_BENCH
+      a.ws = g_tune.variant == 8 ? (float*)g_tune.stamp_buffer : nullptr;   // 1008: main-loop clock stamps (persistent form)
+#endif
+      if constexpr (EPI == MJV_EPI_BIAS || EPI == MJV_EPI_BIAS_RELU || EPI == MJV_EPI_SILU_MUL) {
+        if (L.persistent) {
+          hipLaunchKernelGGL((t256::gemm256p_kernel<EPI>), dim3(L.grid), dim3(512), t256::LDS_BYTES, s, a);
+          return mjv_check_launch("gemm_bf16");
+        }
+      }
+      hipLaunchKernelGGL((t256::gemm256_kernel<EPI, 0>), dim3(L.grid), dim3(512), LDS1, s, a);
+    }
+  } else if (L.split > 1) {
+    hipLaunchKernelGGL((t128::gemm128_kernel<EPI, true>), dim3(L.grid), dim3(256), t128::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(t128::splitk_finish_kernel<EPI>, dim3(L.tiles_m * L.tiles_n), dim3(256), 0, s, a);
   } else {
-    a.tiles_m = (a.M + 127) / 128;
-    a.tiles_n = (a.N + 127) / 128;
-    const int tiles = a.tiles_m * a.tiles_n;
-    if (a.split > 1) {
-      hipLaunchKernelGGL((t128::gemm128_kernel<EPI, true>), dim3(tiles * a.split), dim3(256), t128::LDS_BYTES, s, a);
-      hipLaunchKernelGGL(t128::splitk_finish_kernel<EPI>, dim3(tiles), dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((t128::gemm128_kernel<EPI, false>), dim3(tiles), dim3(256), t128::LDS_BYTES, s, a);
-    }
+    hipLaunchKernelGGL((t128::gemm128_kernel<EPI, false>), dim3(L.grid), dim3(256), t128::LDS_BYTES, s, a);
   }
   return mjv_check_launch("gemm_bf16");
 }
 
-// the 128 x 256 two-per-CU kernel (tile code 2): K % 32 == 0, N % 8 == 0, plain output rows, bias / bias + GELU / LayerScale + residual
+// the 128 x 256 two-per-CU kernel (tile code 2)
 template <int EPI>
-int launch_t2(GemmArgs a, hipStream_t s) {
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)t2::gemm2_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, t2::LDS_BYTES);
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  a.tiles_m = (a.M + t2::BM - 1) / t2::BM;
-  a.tiles_n = (a.N + t2::BN - 1) / t2::BN;
-  hipLaunchKernelGGL((t2::gemm2_kernel<EPI>), dim3(a.tiles_m * a.tiles_n), dim3(256), t2::LDS_BYTES, s, a);
+int launch_t2(GemmArgs a, const GemmLaunch& L, hipStream_t s) {
+  static MjvOncePerDevice once;
+  once([] { MJV_MAX_LDS(t2::gemm2_kernel<EPI>, t2::LDS_BYTES); });
+  a.tiles_m = L.tiles_m, a.tiles_n = L.tiles_n;
+  hipLaunchKernelGGL((t2::gemm2_kernel<EPI>), dim3(L.grid), dim3(256), t2::LDS_BYTES, s, a);
   return mjv_check_launch("gemm_bf16");
+}
+
+// check, then plan against `cus` compute units (<= 0: those of THIS device - partitioned parts differ)
+int checked_plan(const mjv_gemm_desc* d, int cus, GemmPlan* plan) {
+  MJV_REQUIRE(d && d->A && d->W && d->C, "gemm: null pointer");
+  MJV_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
+  MJV_REQUIRE(d->tile == 0 || d->tile == 2 || d->tile == 64 || d->tile == 128 || d->tile == 256, "gemm: tile %d not in {0, 2, 64, 128, 256}", d->tile);
+  if (d->a_format != MJV_FMT_BF16 || d->w_format != MJV_FMT_BF16) {
+    if (int rc = mjv_gemm_mxfp8_check(d)) return rc;   // gemm_fp8.hip
+    return mjv_gemm_plan_build(d, cus > 0 ? cus : mjv_device_cus(), g_tune, plan);
+  }
+  MJV_REQUIRE(d->c_format == MJV_FMT_BF16, "gemm: an MXFP8 output needs MXFP8 operands");
+  MJV_REQUIRE(d->K % 64 == 0, "gemm: K=%d must be a multiple of 64", d->K);
+  MJV_REQUIRE(d->N % 8 == 0, "gemm: N=%d must be a multiple of 8", d->N);
+  MJV_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 4 == 0, "gemm: leading dims must be multiples of 8");
+  MJV_REQUIRE(d->lda >= d->K && d->ldw >= d->K, "gemm: lda/ldw smaller than K");
+  MJV_REQUIRE(((uintptr_t)d->A | (uintptr_t)d->W) % 16 == 0 && (uintptr_t)d->C % 8 == 0, "gemm: misaligned pointer");
+  if (d->epilogue == MJV_EPI_SCALE_RES) {
+    MJV_REQUIRE(d->res != nullptr && d->ldr % 4 == 0, "gemm: SCALE_RES needs a residual");
+  }
+  if (d->epilogue == MJV_EPI_SILU_MUL) {
+    MJV_REQUIRE(d->N % 32 == 0 && d->bias == nullptr, "gemm: SILU_MUL needs N %% 32 == 0 and no bias");
+  }
+  if (d->epilogue == MJV_EPI_ROPE_QKV) {
+    // (rope_group 0, ABI 6: a k | v projection without q heads - the last decoder layer of a scorer needs q for a few rows only)
+    MJV_REQUIRE(d->rope_cos && d->rope_sin && d->rope_pos && d->rope_k && d->rope_group >= 0 && (d->rope_q || d->rope_group == 0),
+                "gemm: ROPE_QKV needs cos / sin / positions / k / group >= 0 (and q unless group == 0)");
+    MJV_REQUIRE(d->N % ((d->rope_group + 2) * 128) == 0 && d->bias == nullptr && !d->out_rows && d->out_group <= 0,
+                "gemm: ROPE_QKV needs N %% ((group + 2) * 128) == 0, no bias, plain output rows");
+    MJV_REQUIRE(d->rope_ldq % 8 == 0 && d->rope_ldk % 8 == 0 && ((uintptr_t)d->rope_q | (uintptr_t)d->rope_k |
+                (uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) % 16 == 0, "gemm: ROPE_QKV alignment");
+  }
+  if (d->row_scale) {
+    MJV_REQUIRE((d->row_shift != nullptr) == (d->col_shift != nullptr) && (d->row_shift != nullptr) == (d->bias_f32 != nullptr),
+                "gemm: row_shift, col_shift and bias_f32 go together (a folded LayerNorm) or not at all (a folded RMSNorm)");
+    MJV_REQUIRE(!d->row_shift || !d->bias, "gemm: a folded LayerNorm carries its bias in bias_f32");
+    MJV_REQUIRE(d->epilogue != MJV_EPI_SCALE_RES, "gemm: no norm is folded into the residual epilogue");
+    MJV_REQUIRE(((uintptr_t)d->row_scale | (uintptr_t)d->row_shift | (uintptr_t)d->col_shift | (uintptr_t)d->bias_f32) % 16 == 0,
+                "gemm: row / column vectors must be 16-byte aligned");
+  } else {
+    MJV_REQUIRE(!d->row_shift && !d->col_shift && !d->bias_f32, "gemm: row_shift / col_shift / bias_f32 need row_scale");
+  }
+  return mjv_gemm_plan_build(d, cus > 0 ? cus : mjv_device_cus(), g_tune, plan);
 }
 
 }  // namespace
 
-// Group-M per shape class, from sweeps on the model's shapes (tools/gemm_bench.py 2003 ... 2016, best of 6 rounds, two
-// boxes): the short-K vision GEMMs prefer 5-7 (qkv +2.8 %, proj +6 %, fc1 +2.5 % over 8 - with N = 1024 and GM = 8 a group
-// is exactly the 32 tiles one XCD runs at a time, and all eight XCDs then walk the same four weight panels in step), the
-// K = 8192 GEMM prefers 4 (+1.6 ... +3.8 %) and so does the 16384-column w1|w3 GEMM (+1.7 %), everything between is flat
-// within 1 % and keeps 8.  (Powers of two - 4, 8 - are the worst choices for the K = 1024 shapes on both main loops.)
-static int pick_gm(int N, int K) { return K <= 1024 ? 5 : (K >= 8192 || N >= 8192) ? 4 : 8; }
-
 extern "C" int64_t mjv_gemm_workspace_bytes(void) { return 256L * 262144L; }
+
+extern "C" int64_t mjv_gemm_plan(const mjv_gemm_desc* d, int32_t cus, int32_t* out, int64_t out_ints) {
+  GemmPlan plan;
+  if (int rc = checked_plan(d, cus, &plan)) return rc;
+  const int64_t n = 4 + 8 * plan.n;
+  if (!out) return n;
+  MJV_REQUIRE(out_ints >= n, "gemm_plan: %ld ints given, %ld needed", (long)out_ints, (long)n);
+  for (int v : {plan.n, plan.gm, plan.nt_store, 0}) *out++ = v;
+  for (const GemmLaunch* L = plan.l; L != plan.l + plan.n; ++L)
+    for (int v : {L->family, L->epilogue, L->row0, L->rows, L->split, L->grid, L->persistent, L->rope_split_after}) *out++ = v;
+  return n;
+}
 
 #ifdef MJV_BENCH
 // measurement switches of the bench library (include/mjv_bench.h); process-wide, never part of the product build
@@ -1795,191 +1772,52 @@ extern "C" int mjv_bench_gemm_stamp_buffer(void* p) {
 }
 #endif
 
+// check, plan (gemm_plan.h), then one pass over the plan's launches
 extern "C" int mjv_gemm_bf16(const mjv_gemm_desc* d, void* stream) {
-  MJV_REQUIRE(d && d->A && d->W && d->C, "gemm: null pointer");
-  MJV_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
-  MJV_REQUIRE(d->tile == 0 || d->tile == 2 || d->tile == 64 || d->tile == 128 || d->tile == 256, "gemm: tile %d not in {0, 2, 64, 128, 256}", d->tile);
-  if (d->a_format != MJV_FMT_BF16 || d->w_format != MJV_FMT_BF16) return mjv_gemm_mxfp8_dispatch(d, stream);   // gemm_fp8.hip
-  MJV_REQUIRE(d->c_format == MJV_FMT_BF16, "gemm: an MXFP8 output needs MXFP8 operands");
-  const int force_tile = d->tile;
-  MJV_REQUIRE(d->K % 64 == 0, "gemm: K=%d must be a multiple of 64", d->K);
-  MJV_REQUIRE(d->N % 8 == 0, "gemm: N=%d must be a multiple of 8", d->N);
-  MJV_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 4 == 0, "gemm: leading dims must be multiples of 8");
-  MJV_REQUIRE(d->lda >= d->K && d->ldw >= d->K, "gemm: lda/ldw smaller than K");
-  MJV_REQUIRE(((uintptr_t)d->A | (uintptr_t)d->W) % 16 == 0 && (uintptr_t)d->C % 8 == 0, "gemm: misaligned pointer");
-  if (d->epilogue == MJV_EPI_SCALE_RES) {
-    MJV_REQUIRE(d->res != nullptr && d->ldr % 4 == 0, "gemm: SCALE_RES needs a residual");
-  }
-  if (d->epilogue == MJV_EPI_SILU_MUL) {
-    MJV_REQUIRE(d->N % 32 == 0 && d->bias == nullptr, "gemm: SILU_MUL needs N %% 32 == 0 and no bias");
-  }
-  if (d->epilogue == MJV_EPI_ROPE_QKV) {
-    // (rope_group 0, ABI 6: a k | v projection without q heads - the last decoder layer of a scorer needs q for a few rows only)
-    MJV_REQUIRE(d->rope_cos && d->rope_sin && d->rope_pos && d->rope_k && d->rope_group >= 0 && (d->rope_q || d->rope_group == 0),
-                "gemm: ROPE_QKV needs cos / sin / positions / k / group >= 0 (and q unless group == 0)");
-    MJV_REQUIRE(d->N % ((d->rope_group + 2) * 128) == 0 && d->bias == nullptr && !d->out_rows && d->out_group <= 0,
-                "gemm: ROPE_QKV needs N %% ((group + 2) * 128) == 0, no bias, plain output rows");
-    MJV_REQUIRE(d->rope_ldq % 8 == 0 && d->rope_ldk % 8 == 0 && ((uintptr_t)d->rope_q | (uintptr_t)d->rope_k |
-                (uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) % 16 == 0, "gemm: ROPE_QKV alignment");
-  }
+  GemmPlan plan;
+  if (int rc = checked_plan(d, 0, &plan)) return rc;
+  if (d->a_format == MJV_FMT_MXFP8) return mjv_gemm_mxfp8_run(d, plan, stream);   // gemm_fp8.hip (the check: both operands are)
   GemmArgs a;
-  a.A = d->A; a.lda = d->lda; a.W = d->W; a.ldw = d->ldw; a.C = d->C; a.ldc = d->ldc;
-  a.M = d->M; a.N = d->N; a.K = d->K;
+  a.W = d->W; a.ldw = d->ldw; a.lda = d->lda; a.C = d->C; a.ldc = d->ldc; a.N = d->N; a.K = d->K;
   a.bias = d->bias; a.scale = d->scale; a.res = d->res; a.ldr = d->ldr;
-  a.res_mod = d->res_mod; a.res_off = d->res_off; a.out_group = d->out_group; a.out_pad = d->out_pad;
-  a.out_rows = d->out_rows;
-  a.tiles_m = a.tiles_n = 0;
-  a.m_base = 0;
-  a.ws = nullptr;
-  a.split = 1;
-  a.gm = MJV_TUNE(gm) > 0 ? MJV_TUNE(gm) : pick_gm(d->N, d->K);
+  a.res_mod = d->res_mod; a.res_off = d->res_off; a.out_group = d->out_group; a.out_pad = d->out_pad; a.out_rows = d->out_rows;
+  a.gm = plan.gm; a.nt_store = plan.nt_store;
   a.rope_cos = d->rope_cos; a.rope_sin = d->rope_sin; a.rope_pos = d->rope_pos; a.rope_q = d->rope_q; a.rope_k = d->rope_k;
   a.rope_ldq = d->rope_ldq; a.rope_ldk = d->rope_ldk; a.rope_group = d->rope_group;
   a.row_scale = d->row_scale; a.row_shift = d->row_shift; a.col_shift = d->col_shift; a.bias_f32 = d->bias_f32;
-  if (d->row_scale) {
-    MJV_REQUIRE((d->row_shift != nullptr) == (d->col_shift != nullptr) && (d->row_shift != nullptr) == (d->bias_f32 != nullptr),
-                "gemm: row_shift, col_shift and bias_f32 go together (a folded LayerNorm) or not at all (a folded RMSNorm)");
-    MJV_REQUIRE(!d->row_shift || !d->bias, "gemm: a folded LayerNorm carries its bias in bias_f32");
-    MJV_REQUIRE(d->epilogue != MJV_EPI_SCALE_RES, "gemm: no norm is folded into the residual epilogue");
-    MJV_REQUIRE(((uintptr_t)d->row_scale | (uintptr_t)d->row_shift | (uintptr_t)d->col_shift | (uintptr_t)d->bias_f32) % 16 == 0,
-                "gemm: row / column vectors must be 16-byte aligned");
-  } else {
-    MJV_REQUIRE(!d->row_shift && !d->col_shift && !d->bias_f32, "gemm: row_shift / col_shift / bias_f32 need row_scale");
-  }
-  // streaming stores for every large output (round 4, once the stores really were nt - see store16: qkv +8 %, proj +4 %,
-  // fc1 +3 %, every other model shape +0.3 ... +0.8 % in tools/gemm_bench.py 7001 7002; in the model, one box, two rounds:
-  // never 93.5 ms per step, K <= 1024 only 92.6, always 92.3 - profiles/r04_g_nt_stores.txt); small outputs, which the next
-  // kernel reads back from the L2, keep plain stores
-  a.nt_store = ((double)d->M * (d->epilogue == MJV_EPI_SILU_MUL ? d->N / 2 : d->N) * 2.0 >= 32.0 * 1024 * 1024) ? 1 : 0;
-  if (MJV_TUNE(nt) >= 0) a.nt_store = MJV_TUNE(nt);
-  const bool big = (force_tile && force_tile != 2) ? force_tile == 256 : (d->M >= 512 && d->N >= 256);
   hipStream_t s = (hipStream_t)stream;
-  g_num_cus = mjv_device_cus();   // tail peeling and split-K plan against the CUs of THIS device (partitioned parts differ)
-  const double flops = 2.0 * d->M * (double)d->N * d->K;
-  // (algorithmic bytes: A and W read once, the output written once - N / 2 columns for the SiLU-mul epilogue)
-  const double bytes = 2.0 * ((double)d->M * d->K + (double)d->N * d->K + (double)d->M * (d->epilogue == MJV_EPI_SILU_MUL ? d->N / 2 : d->N));
-  // Wave quantisation: with one 256x256 workgroup per CU a launch runs in ceil(tiles / 256) rounds, and a last round
-  // that is mostly empty costs a full tile time (M = 17488, N = 2048: 552 tiles = 2.16 rounds -> 3).  When the last
-  // round is under-filled, the trailing m-tile rows are peeled off and run as 128x128 tiles (2 workgroups per CU,
-  // quarter-size work items) in a second launch on the same stream; rows are independent, so results are unchanged.
-  int m_main = d->M;
-  if (big && !force_tile && !d->out_rows) {
-    const int tn = (d->N + 255) / 256, tmx = (d->M + 255) / 256;
-    const int tiles = tn * tmx;
-    const int rem = tiles % g_num_cus;
-    const int rows_main_tiles = (tiles - rem) / tn;  // whole m-tile rows inside the full rounds
-    if (tiles > g_num_cus && rem > 0 && rem * 4 <= g_num_cus * 2 && rows_main_tiles > 0) {
-      m_main = rows_main_tiles * 256;
-      if (m_main >= d->M) m_main = d->M;
-    }
-  }
-  static const char* const tags256[] = {"gemm256_bias", "gemm256_bias_gelu", "gemm256_bias_relu", "gemm256_scale_res",
-                                        "gemm256_silu_mul", "gemm256_rope_qkv"};
-  static const char* const tags256s[] = {"gemm256s_bias", "gemm256s_bias_gelu", "gemm256s_bias_relu", "gemm256s_scale_res",
-                                         "gemm256s_silu_mul"};
-  static const char* const tags128[] = {"gemm128_bias", "gemm128_bias_gelu", "gemm128_bias_relu", "gemm128_scale_res",
-                                        "gemm128_silu_mul"};
-  if (d->epilogue < 0 || d->epilogue > MJV_EPI_ROPE_QKV) {
-    mjv_set_error("gemm: unknown epilogue %d", d->epilogue);
-    return MJV_E_ARG;
-  }
-  // tile 2: the 128 x 256 two-workgroups-per-CU kernel (short-K Linears; every row in ONE launch: its last m-tile may be partial)
-  const bool t2_ok = (d->epilogue == MJV_EPI_BIAS || d->epilogue == MJV_EPI_BIAS_GELU || d->epilogue == MJV_EPI_SCALE_RES) && !d->out_rows &&
-                     d->out_group <= 0 && d->res_mod <= 0 && !d->row_scale && (uintptr_t)d->C % 16 == 0 && d->ldc % 8 == 0 &&
-                     (d->epilogue != MJV_EPI_SCALE_RES || (d->ldr % 8 == 0 && (uintptr_t)d->res % 16 == 0));
-  if (force_tile == 2) {
-    if (!t2_ok) {
-      mjv_set_error("gemm: tile 2 (128 x 256, two workgroups per CU) takes bias / bias + GELU / LayerScale + residual epilogues on plain, "
-                    "16-byte aligned output rows");
-      return MJV_E_UNSUPPORTED;
-    }
-    static const char* const tags2[] = {"gemm2_bias", "gemm2_bias_gelu", "", "gemm2_scale_res"};
-    a.gm = MJV_TUNE(gm) > 0 ? MJV_TUNE(gm) : 8;
-    MjvProfScope ps(tags2[d->epilogue], s, flops, bytes);
-    switch (d->epilogue) {
-      case MJV_EPI_BIAS: return launch_t2<MJV_EPI_BIAS>(a, s);
-      case MJV_EPI_BIAS_GELU: return launch_t2<MJV_EPI_BIAS_GELU>(a, s);
-      default: return launch_t2<MJV_EPI_SCALE_RES>(a, s);
-    }
-  }
-  // one profiler scope per kernel launch, named like the kernel rocprofv3 reports (t256::gemm256_kernel<EPI> / t128::...)
-  // A 128-tile launch with fewer workgroups than the chip holds (the peeled tail rows, the batch-sized head GEMMs) is
-  // bound by each CU's L2->LDS fill rate (about 45 GB/s for one workgroup): its time is the launch's operand traffic
-  // divided by the CUs it occupies.  Splitting K over more workgroups engages the idle CUs; the slices' fp32
-  // accumulators go through the caller's workspace and a second, fully parallel launch sums them in slice order.
-  auto plan_split = [&](GemmArgs& g) {
-    if (!MJV_TUNE(split_k) || !d->workspace) return;
-    const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128), nk = g.K / 64;
-    // measured (tools/gemm_bench.py, MJV_BENCH_TAILS=1): the second launch costs about 5 us, so K = 1024 / 2048 tails lose
-    // 1-5 us while K = 4096 / 8192 tails gain 12 / 25 us (45 -> 33, 89 -> 64)
-    if (tiles >= 2 * g_num_cus || nk < 64) return;
-    int sp = (2 * g_num_cus) / tiles;
-    if (sp > MJV_TUNE(split_max)) sp = MJV_TUNE(split_max);
-    if (sp > nk / 4) sp = nk / 4;
-    if (sp < 2 || (long)tiles * sp * 65536L > d->workspace_bytes) return;
-    g.split = sp;
-    g.ws = (float*)d->workspace;
-  };
-  static const char* const tags64[] = {"gemm64_bias", "gemm64_bias_gelu", "gemm64_bias_relu", "gemm64_scale_res",
-                                       "gemm64_silu_mul"};
-  // Under-filled problems with deep K (K >= 4096: the ~1100-row tail of the language tower's w2, and the whole w2 of a
-  // single-video forward): K slices of 256 x 256 tiles, one workgroup per CU, at most one round - the 256 kernel's main
-  // loop moves 1.4-1.6x the flops per CU-second of the 128 kernel's, which pays for the fp32 round trip of the slices
-  // (tools/gemm_bench.py, MJV_BENCH_TAILS=1: 1104 x 2048 x 8192 in 56 us against 64 us on sliced 128 tiles and 141 us on
-  // unsliced 256 tiles; 2186 rows: 83 against 145 us).  At K = 2048 it is a wash or a loss (wqkv tail 41 -> 44 us): not used.
-  auto plan_split256 = [&](GemmArgs& g) -> bool {
-    if (!MJV_TUNE(split256) || force_tile || !d->workspace || d->out_rows) return false;
-    const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256), nk = g.K / 64;
-    // (a last m-tile that is mostly empty wastes its share of every slice: 138 rows x 16384 columns ran 10 % slower sliced)
-    const bool filled = (long)g.M * 10 >= (long)((g.M + 255) / 256) * 256 * 7;
-    if (g.M <= MJV_TUNE(skinny_max_m) || g.N < 256 || nk < MJV_TUNE(split256_min_nk) || tiles * 2 > g_num_cus || !filled) return false;
-    int sp = g_num_cus / tiles;
-    if (sp > MJV_TUNE(split_max)) sp = MJV_TUNE(split_max);
-    if (sp > nk / MJV_TUNE(split256_min_kt)) sp = nk / MJV_TUNE(split256_min_kt);
-    if (sp < 2 || (long)tiles * sp * 262144L > d->workspace_bytes) return false;
-    g.split = sp;
-    g.ws = (float*)d->workspace;
-    return true;
-  };
-  auto run = [&](GemmArgs g, bool use_big) -> int {
-    if (plan_split256(g)) use_big = true;
-    // skinny problems (peeled tails of a few dozen rows, batch-sized head layers): the 64 x 32 kernel
-    const bool skinny = !use_big && (force_tile ? force_tile == 64 : g.M <= MJV_TUNE(skinny_max_m));
-    if (!use_big && !skinny) plan_split(g);
-    const double frac = (double)g.M / (double)d->M;
-    // the rotary epilogue needs a whole 256-column tile staged in LDS: only the unsplit 256^2 kernel has it.  Rows that run
-    // on the other kernels (peeled tails, small problems) get the plain Linear into C and the standalone rope_split kernel.
-    const int epi = (d->epilogue == MJV_EPI_ROPE_QKV && (!use_big || g.split > 1)) ? (int)MJV_EPI_BIAS : d->epilogue;
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmLaunch& L = plan.l[i];
+    // rows [row0, row0 + rows): the kernel indexes A relative to the shifted pointer and adds m_base back for the output /
+    // residual row maps, which depend on the absolute row
+    const long r0 = L.row0;
+    a.A = d->A + r0 * d->lda; a.M = L.rows; a.m_base = L.row0;
+    a.split = L.split; a.ws = L.split > 1 ? (float*)d->workspace : nullptr;
     int rc;
     {
-      MjvProfScope ps(use_big ? (g.split > 1 ? tags256s[epi] : tags256[epi]) : skinny ? tags64[epi] : tags128[epi], s, flops * frac, bytes * frac);
-      switch (epi) {
-        case MJV_EPI_BIAS: rc = launch<MJV_EPI_BIAS>(g, s, use_big, skinny); break;
-        case MJV_EPI_BIAS_GELU: rc = launch<MJV_EPI_BIAS_GELU>(g, s, use_big, skinny); break;
-        case MJV_EPI_BIAS_RELU: rc = launch<MJV_EPI_BIAS_RELU>(g, s, use_big, skinny); break;
-        case MJV_EPI_SCALE_RES: rc = launch<MJV_EPI_SCALE_RES>(g, s, use_big, skinny); break;
-        case MJV_EPI_ROPE_QKV: rc = launch<MJV_EPI_ROPE_QKV>(g, s, true, false); break;   // unsplit 256 kernel only
-        default: rc = launch<MJV_EPI_SILU_MUL>(g, s, use_big, skinny); break;
+      MjvProfScope ps(L.tag, s, plan.flops * L.frac, plan.bytes * L.frac);   // one profiler scope per kernel launch
+      if (L.family == 2) {
+        switch (L.epilogue) {
+          case MJV_EPI_BIAS: rc = launch_t2<MJV_EPI_BIAS>(a, L, s); break;
+          case MJV_EPI_BIAS_GELU: rc = launch_t2<MJV_EPI_BIAS_GELU>(a, L, s); break;
+          default: rc = launch_t2<MJV_EPI_SCALE_RES>(a, L, s); break;
+        }
+      } else {
+        switch (L.epilogue) {
+          case MJV_EPI_BIAS: rc = launch<MJV_EPI_BIAS>(a, L, s); break;
+          case MJV_EPI_BIAS_GELU: rc = launch<MJV_EPI_BIAS_GELU>(a, L, s); break;
+          case MJV_EPI_BIAS_RELU: rc = launch<MJV_EPI_BIAS_RELU>(a, L, s); break;
+          case MJV_EPI_SCALE_RES: rc = launch<MJV_EPI_SCALE_RES>(a, L, s); break;
+          case MJV_EPI_ROPE_QKV: rc = launch<MJV_EPI_ROPE_QKV>(a, L, s); break;   // unsliced 256 kernel only
+          default: rc = launch<MJV_EPI_SILU_MUL>(a, L, s); break;
+        }
       }
     }
-    if (rc == MJV_OK && epi != d->epilogue) {
-      const long r0 = g.m_base;
-      rc = mjv_rope_split_bf16(d->C + r0 * d->ldc, d->ldc, d->rope_q + r0 * d->rope_ldq, d->rope_ldq,
-                               d->rope_k + r0 * d->rope_ldk, d->rope_ldk, d->rope_cos, d->rope_sin, d->rope_pos + r0, g.M,
-                               d->N / ((d->rope_group + 2) * 128), d->rope_group, stream);
-    }
-    return rc;
-  };
-  if (m_main == d->M) return run(a, big);
-  GemmArgs head = a;
-  head.M = m_main;
-  int rc = run(head, true);
-  if (rc) return rc;
-  // tail rows [m_main, M): the kernel indexes A relative to the shifted pointer and adds m_base back for the output /
-  // residual row maps, which depend on the absolute row
-  GemmArgs tail = a;
-  tail.M = d->M - m_main;
-  tail.A = a.A + (long)m_main * a.lda;
-  tail.m_base = m_main;
-  return run(tail, false);
+    if (rc == MJV_OK && L.rope_split_after)
+      rc = mjv_rope_split_bf16(d->C + r0 * d->ldc, d->ldc, d->rope_q + r0 * d->rope_ldq, d->rope_ldq, d->rope_k + r0 * d->rope_ldk,
+                               d->rope_ldk, d->rope_cos, d->rope_sin, d->rope_pos + r0, L.rows, d->N / ((d->rope_group + 2) * 128),
+                               d->rope_group, stream);
+    if (rc) return rc;
+  }
+  return MJV_OK;
 }

@@ -21,12 +21,11 @@
 // separate quantise pass and at half the store bytes.
 //
 // Round 5: (i) the m-tile rows of an under-filled last round, and launches that under-fill the chip as a whole, run K-SLICED
-// (gemm256f8_kernel<.., SPLIT> writes fp32 accumulator images, splitk_finish256f8_kernel sums them in slice order and runs
-// every epilogue incl. the block quantiser) - mjv_gemm_mxfp8_dispatch plans it like gemm.hip plans the bf16 tails; (ii) the
-// GELU epilogue takes the split-table form of gemm.hip's round-4 pass A (G8_* below).
+// (gemm256f8_kernel<.., SPLIT> writes fp32 accumulator images, splitk_finish256f8_kernel sums them in slice order and runs every
+// epilogue incl. the block quantiser; planned in gemm_plan.h); (ii) the GELU epilogue takes gemm.hip's split-table form (G8_*).
 #include "mx8.h"
 #include "gemm_common.h"
-#include <atomic>
+#include "gemm_plan.h"
 
 namespace {
 
@@ -525,37 +524,25 @@ __global__ __launch_bounds__(256) void splitk_finish256f8_kernel(Gemm8Args p) {
 }
 
 template <int EPI, bool OUT8>
-int launch8(Gemm8Args a, hipStream_t s) {
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-    (void)hipFuncSetAttribute((const void*)gemm256f8_kernel<EPI, OUT8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done.fetch_or(bit, std::memory_order_release);
-  }
-  a.tiles_m = (a.M + 255) / 256;
-  a.tiles_n = (a.N + 255) / 256;
-  if (a.split > 1) {
-    static std::atomic<unsigned long long> attr_split{0};
-    if (!(attr_split.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute((const void*)gemm256f8_kernel<MJV_EPI_BIAS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      attr_split.fetch_or(bit, std::memory_order_release);
-    }
-    const int tiles = a.tiles_m * a.tiles_n;
+int launch8(Gemm8Args a, const GemmLaunch& L, hipStream_t s) {
+  static MjvOncePerDevice once, once_split;
+  once([] { MJV_MAX_LDS((gemm256f8_kernel<EPI, OUT8>), LDS_BYTES); });
+  a.tiles_m = L.tiles_m, a.tiles_n = L.tiles_n;
+  if (L.split > 1) {
+    once_split([] { MJV_MAX_LDS((gemm256f8_kernel<MJV_EPI_BIAS, false, true>), LDS_BYTES); });
     constexpr int CB = (EPI == MJV_EPI_SILU_MUL) ? 1 : 2;
-    hipLaunchKernelGGL((gemm256f8_kernel<MJV_EPI_BIAS, false, true>), dim3(tiles * a.split), dim3(512), LDS_BYTES, s, a);
-    hipLaunchKernelGGL((splitk_finish256f8_kernel<EPI, OUT8>), dim3(tiles * 16 * CB), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gemm256f8_kernel<MJV_EPI_BIAS, false, true>), dim3(L.grid), dim3(512), LDS_BYTES, s, a);
+    hipLaunchKernelGGL((splitk_finish256f8_kernel<EPI, OUT8>), dim3(L.tiles_m * L.tiles_n * 16 * CB), dim3(256), 0, s, a);
     return mjv_check_launch("gemm_mxfp8 (K-sliced)");
   }
-  hipLaunchKernelGGL((gemm256f8_kernel<EPI, OUT8>), dim3(a.tiles_m * a.tiles_n), dim3(512), LDS_BYTES, s, a);
+  hipLaunchKernelGGL((gemm256f8_kernel<EPI, OUT8>), dim3(L.grid), dim3(512), LDS_BYTES, s, a);
   return mjv_check_launch("gemm_mxfp8");
 }
 
 }  // namespace
 
-// called by mjv_gemm_bf16 (gemm.hip) when the descriptor names MXFP8 operands
-int mjv_gemm_mxfp8_dispatch(const mjv_gemm_desc* d, void* stream) {
+// the descriptor checks of MXFP8 operands (mjv_gemm_bf16, gemm.hip, has checked pointers, sizes and the tile code)
+int mjv_gemm_mxfp8_check(const mjv_gemm_desc* d) {
   MJV_REQUIRE(d->a_format == MJV_FMT_MXFP8 && d->w_format == MJV_FMT_MXFP8, "gemm: A and W must both be MXFP8 (or both bf16)");
   MJV_REQUIRE(d->a_scales && d->w_scales, "gemm(mxfp8): null scale pointer");
   MJV_REQUIRE(d->K % 128 == 0, "gemm(mxfp8): K=%d must be a multiple of 128", d->K);
@@ -566,85 +553,51 @@ int mjv_gemm_mxfp8_dispatch(const mjv_gemm_desc* d, void* stream) {
   MJV_REQUIRE(d->epilogue >= MJV_EPI_BIAS && d->epilogue <= MJV_EPI_SILU_MUL, "gemm(mxfp8): epilogue %d unsupported", d->epilogue);
   const bool out8 = d->c_format == MJV_FMT_MXFP8;
   MJV_REQUIRE(d->c_format == MJV_FMT_BF16 || out8, "gemm(mxfp8): c_format %d", d->c_format);
-  const int nout = d->epilogue == MJV_EPI_SILU_MUL ? d->N / 2 : d->N;
   if (out8) {
     MJV_REQUIRE(d->epilogue != MJV_EPI_SCALE_RES, "gemm(mxfp8): the residual epilogue has no MXFP8 output");
-    MJV_REQUIRE(d->c_scales && nout % 128 == 0 && d->ldc % 8 == 0 && (uintptr_t)d->C % 8 == 0, "gemm(mxfp8): MXFP8 output needs scales, width %% 128 == 0");
+    MJV_REQUIRE(d->c_scales && gemm_out_cols(d) % 128 == 0 && d->ldc % 8 == 0 && (uintptr_t)d->C % 8 == 0, "gemm(mxfp8): MXFP8 output needs scales, width %% 128 == 0");
   } else {
     MJV_REQUIRE(d->ldc % 8 == 0 && (uintptr_t)d->C % 16 == 0, "gemm(mxfp8): ldc / C alignment");
   }
   if (d->epilogue == MJV_EPI_SCALE_RES) MJV_REQUIRE(d->res != nullptr && d->ldr % 8 == 0, "gemm(mxfp8): SCALE_RES needs a residual");
   if (d->epilogue == MJV_EPI_SILU_MUL) MJV_REQUIRE(d->N % 32 == 0 && d->bias == nullptr, "gemm(mxfp8): SILU_MUL needs N %% 32 == 0 and no bias");
+  return MJV_OK;
+}
+
+// executes the plan of a checked descriptor (gemm_plan.h: the peeled tail, the K slices)
+int mjv_gemm_mxfp8_run(const mjv_gemm_desc* d, const GemmPlan& plan, void* stream) {
+  const bool out8 = d->c_format == MJV_FMT_MXFP8;
   Gemm8Args a;
-  a.A = (const uint8_t*)d->A; a.lda = d->lda; a.W = (const uint8_t*)d->W; a.ldw = d->ldw;
-  a.As = d->a_scales; a.a_groups = (d->M + 63) / 64; a.Ws = d->w_scales; a.w_groups = (d->N + 63) / 64;
-  a.a_grp_max = a.a_groups - 1;
-  a.C = d->C; a.ldc = d->ldc; a.Cs = d->c_scales; a.c_groups = (d->M + 63) / 64;
-  a.M = d->M; a.N = d->N; a.K = d->K;
-  a.bias = d->bias; a.scale = d->scale; a.res = d->res; a.ldr = d->ldr;
-  a.tiles_m = a.tiles_n = 0;
-  a.ws = nullptr; a.split = 1;
-  a.gm = d->K <= 2048 ? 5 : (d->K >= 16384 || d->N >= 8192) ? 4 : 8;   // (gemm.hip pick_gm by K BYTES per row)
-  a.nt_store = ((double)d->M * nout * (out8 ? 1.0 : 2.0) >= 32.0 * 1024 * 1024) ? 1 : 0;   // (gemm.hip: streaming stores for large outputs)
+  a.lda = d->lda; a.W = (const uint8_t*)d->W; a.ldw = d->ldw;
+  a.a_groups = (d->M + 63) / 64; a.Ws = d->w_scales; a.w_groups = (d->N + 63) / 64;
+  a.ldc = d->ldc; a.c_groups = (d->M + 63) / 64;
+  a.N = d->N; a.K = d->K;
+  a.bias = d->bias; a.scale = d->scale; a.ldr = d->ldr;
+  a.gm = plan.gm; a.nt_store = plan.nt_store;
   hipStream_t s = (hipStream_t)stream;
-  static const char* const tags[] = {"gemm256f8_bias", "gemm256f8_bias_gelu", "gemm256f8_bias_relu", "gemm256f8_scale_res", "gemm256f8_silu_mul"};
-  static const char* const tags_s[] = {"gemm256f8s_bias", "gemm256f8s_bias_gelu", "gemm256f8s_bias_relu", "gemm256f8s_scale_res", "gemm256f8s_silu_mul"};
-  const double flops = 2.0 * d->M * (double)d->N * d->K;
-  const double bytes = 1.03 * ((double)d->M * d->K + (double)d->N * d->K) + (out8 ? 1.03 : 2.0) * (double)d->M * nout;
-  auto run = [&](const Gemm8Args& g, double frac) -> int {
-    MjvProfScope ps(g.split > 1 ? tags_s[d->epilogue] : tags[d->epilogue], s, flops * frac, bytes * frac);
-    switch (d->epilogue) {
-      case MJV_EPI_BIAS: return out8 ? launch8<MJV_EPI_BIAS, true>(g, s) : launch8<MJV_EPI_BIAS, false>(g, s);
-      case MJV_EPI_BIAS_GELU: return out8 ? launch8<MJV_EPI_BIAS_GELU, true>(g, s) : launch8<MJV_EPI_BIAS_GELU, false>(g, s);
-      case MJV_EPI_BIAS_RELU: return out8 ? launch8<MJV_EPI_BIAS_RELU, true>(g, s) : launch8<MJV_EPI_BIAS_RELU, false>(g, s);
-      case MJV_EPI_SCALE_RES: return launch8<MJV_EPI_SCALE_RES, false>(g, s);
-      default: return out8 ? launch8<MJV_EPI_SILU_MUL, true>(g, s) : launch8<MJV_EPI_SILU_MUL, false>(g, s);
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmLaunch& L = plan.l[i];
+    // rows [row0, row0 + rows): every row-indexed pointer moves down row0 rows (row0 / 64 whole scale groups: row0 % 256 == 0; the
+    // group COUNTS, which are the scale buffers' strides, stay those of the whole matrix)
+    const long r0 = L.row0, g0 = r0 / 64;
+    a.M = L.rows;
+    a.A = (const uint8_t*)d->A + r0 * d->lda;
+    a.As = d->a_scales + g0 * 256;
+    a.a_grp_max = a.a_groups - 1 - g0;
+    a.C = (uint8_t*)d->C + r0 * d->ldc * (out8 ? 1 : 2);
+    a.Cs = d->c_scales ? d->c_scales + g0 * 256 : nullptr;
+    a.res = d->res ? d->res + r0 * d->ldr : nullptr;
+    a.split = L.split; a.ws = L.split > 1 ? (float*)d->workspace : nullptr;
+    MjvProfScope ps(L.tag, s, plan.flops * L.frac, plan.bytes * L.frac);
+    int rc;
+    switch (L.epilogue) {
+      case MJV_EPI_BIAS: rc = out8 ? launch8<MJV_EPI_BIAS, true>(a, L, s) : launch8<MJV_EPI_BIAS, false>(a, L, s); break;
+      case MJV_EPI_BIAS_GELU: rc = out8 ? launch8<MJV_EPI_BIAS_GELU, true>(a, L, s) : launch8<MJV_EPI_BIAS_GELU, false>(a, L, s); break;
+      case MJV_EPI_BIAS_RELU: rc = out8 ? launch8<MJV_EPI_BIAS_RELU, true>(a, L, s) : launch8<MJV_EPI_BIAS_RELU, false>(a, L, s); break;
+      case MJV_EPI_SCALE_RES: rc = launch8<MJV_EPI_SCALE_RES, false>(a, L, s); break;
+      default: rc = out8 ? launch8<MJV_EPI_SILU_MUL, true>(a, L, s) : launch8<MJV_EPI_SILU_MUL, false>(a, L, s); break;
     }
-  };
-  // Wave quantisation (gemm.hip does the same for the bf16 kernels): one 256 x 256 workgroup per CU, so a launch runs in
-  // ceil(tiles / CUs) rounds and a last round that is mostly empty costs a full tile time - the 64-row tail of the vision
-  // tower's 65 600 rows is a 17th round of 16 tiles after fc1's 16 full ones, w2's 552 tiles are 2.16 rounds.  With a
-  // workspace, the m-tile rows of an under-filled last round are peeled off and run K-SLICED over all CUs (fp32 slices
-  // through the workspace, summed in slice order by splitk_finish256f8_kernel: deterministic); an under-filled launch as a
-  // whole (few rows: one video per forward) is sliced the same way.  Rows are independent and 64-row scale groups stay whole
-  // (m_main % 256 == 0): results differ from the unsliced launch by fp32 re-association only.
-  const int cus = mjv_device_cus();
-  const int tn = (d->N + 255) / 256, tmx = (d->M + 255) / 256;
-  const int tiles = tn * tmx, nk = d->K / BK;
-  auto plan_split = [&](Gemm8Args& g) {
-    if (!d->workspace || nk < 8) return;     // (K < 1024: two launches cost more than the idle CUs)
-    const int t = ((g.M + 255) / 256) * tn;
-    int sp = cus / t;
-    if (sp > nk / 2) sp = nk / 2;            // at least two K-tiles per slice (the pipeline's prologue fills two)
-    if (sp > 32) sp = 32;
-    if (sp < 2 || (long)t * sp * 262144L > d->workspace_bytes) return;
-    g.split = sp;
-    g.ws = (float*)d->workspace;
-  };
-  int m_main = d->M;
-  if (d->workspace && d->tile == 0) {
-    const int rem = tiles % cus;
-    const int rows_main_tiles = (tiles - rem) / tn;   // whole m-tile rows inside the full rounds
-    if (nk >= 8 && tiles > cus && rem > 0 && rem * 2 <= cus && rows_main_tiles > 0 && rows_main_tiles * 256 < d->M) m_main = rows_main_tiles * 256;
+    if (rc) return rc;
   }
-  if (m_main == d->M) {
-    if (tiles * 2 <= cus && d->tile == 0) plan_split(a);
-    return run(a, 1.0);
-  }
-  Gemm8Args head = a;
-  head.M = m_main;
-  int rc = run(head, (double)m_main / d->M);
-  if (rc) return rc;
-  // tail rows [m_main, M): every row-indexed pointer moves down m_main rows (m_main / 64 whole scale groups; the group COUNTS,
-  // which are the scale buffers' strides, stay those of the whole matrix)
-  Gemm8Args tail = a;
-  tail.M = d->M - m_main;
-  tail.A = a.A + (long)m_main * a.lda;
-  tail.As = a.As + (long)(m_main / 64) * 256;
-  tail.a_grp_max = a.a_groups - 1 - m_main / 64;
-  tail.C = out8 ? (void*)((uint8_t*)a.C + (long)m_main * a.ldc) : (void*)((u16*)a.C + (long)m_main * a.ldc);
-  if (a.Cs) tail.Cs = a.Cs + (long)(m_main / 64) * 256;
-  if (a.res) tail.res = a.res + (long)m_main * a.ldr;
-  plan_split(tail);
-  return run(tail, (double)tail.M / d->M);
+  return MJV_OK;
 }

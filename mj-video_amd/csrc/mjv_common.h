@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include "mjv.h"
 
 typedef uint16_t u16;
@@ -75,8 +76,26 @@ void mjv_set_error(const char* fmt, ...);
 int mjv_check_launch(const char* what);
 int mjv_device_cus();   // multiProcessorCount of the current device (cached per device)
 
-// MXFP8 operands (gemm_fp8.hip); mjv_gemm_bf16 hands descriptors that name them over
-int mjv_gemm_mxfp8_dispatch(const mjv_gemm_desc* d, void* stream);
+// The dynamic-LDS limit is a per-device function attribute: a launch site keeps one of these (static) and sets the attributes
+// of the kernels it launches once on every device it runs on.  Racing first calls both set them: idempotent.
+struct MjvOncePerDevice {
+  std::atomic<unsigned long long> done{0};
+  template <class F>
+  void operator()(F&& set_attributes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return;
+    set_attributes();
+    done.fetch_or(bit, std::memory_order_release);
+  }
+};
+#define MJV_MAX_LDS(kernel, bytes) (void)hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
+
+// MXFP8 operands (gemm_fp8.hip): mjv_gemm_bf16 (gemm.hip) checks, plans (gemm_plan.h) and hands descriptors that name them over
+struct GemmPlan;
+int mjv_gemm_mxfp8_check(const mjv_gemm_desc* d);
+int mjv_gemm_mxfp8_run(const mjv_gemm_desc* d, const GemmPlan& plan, void* stream);
 
 // profiler hooks (capi.cpp)
 struct MjvProfScope {

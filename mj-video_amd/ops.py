@@ -112,7 +112,25 @@ def set_gemm_workspace(ws: Optional[torch.Tensor]) -> None:
     _tls.gemm_ws = ws
 
 
-def _gemm_mxfp8(a: MX8, w: MX8, out, epilogue: int, bias, scale, res, M: Optional[int], workspace=None, tile=None):
+def gemm_desc_plan(d: GemmDesc, cus: int = 0) -> dict:
+    """``mjv_gemm_plan`` (include/mjv.h) of a filled descriptor: what ``mjv_gemm_bf16`` would launch for it on ``cus`` compute
+    units (0: the current device) - ``dict(gm, nt_store, launches=[dict(family, epilogue, row0, rows, split, grid, persistent,
+    rope_split_after), ...])``.  Reads no device memory and launches nothing: works without a GPU when ``cus`` is given."""
+    lib = load_library()
+    n = int(lib.mjv_gemm_plan(C.byref(d), cus, None, 0))
+    check(min(0, n), "mjv_gemm_plan")
+    buf = (C.c_int32 * n)()
+    check(min(0, int(lib.mjv_gemm_plan(C.byref(d), cus, buf, n))), "mjv_gemm_plan")
+    keys = ("family", "epilogue", "row0", "rows", "split", "grid", "persistent", "rope_split_after")
+    return dict(gm=buf[1], nt_store=buf[2], launches=[dict(zip(keys, buf[4 + 8 * i:12 + 8 * i])) for i in range(buf[0])])
+
+
+def gemm_plan(*args, cus: int = 0, **kw) -> dict:
+    """the plan (``gemm_desc_plan``) of the launches ``gemm(*args, **kw)`` would make; nothing runs"""
+    return gemm(*args, _plan_cus=cus, **kw)
+
+
+def _gemm_mxfp8(a: MX8, w: MX8, out, epilogue: int, bias, scale, res, M: Optional[int], workspace=None, tile=None, _plan_cus=None):
     """MXFP8 operands (include/mjv.h, ABI 5): ``out`` a bf16 tensor or an ``MX8`` (the epilogue's result block-quantised)."""
     assert isinstance(w, MX8), "MXFP8 activations need MXFP8 weights"
     _chk_bf16(bias, scale, res)
@@ -145,6 +163,8 @@ def _gemm_mxfp8(a: MX8, w: MX8, out, epilogue: int, bias, scale, res, M: Optiona
     if d.tile not in (0, 256):
         d.tile = 256    # (one tile kernel exists for MXFP8 operands: the parity tests' tile sweep maps onto it)
     with torch.cuda.device(dev):
+        if _plan_cus is not None:
+            return gemm_desc_plan(d, _plan_cus)
         check(load_library().mjv_gemm_bf16(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "mjv_gemm_bf16(mxfp8)")
     return out
 
@@ -154,7 +174,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EP
          res: Optional[torch.Tensor] = None, res_mod: int = 0, res_off: int = 0, out_group: int = 0,
          out_pad: int = 0, out_rows: Optional[torch.Tensor] = None, M: Optional[int] = None,
          rope: Optional[tuple] = None, workspace: Optional[torch.Tensor] = None, tile: Optional[int] = None,
-         folded_norm: Optional[tuple] = None) -> torch.Tensor:
+         folded_norm: Optional[tuple] = None, _plan_cus: Optional[int] = None) -> torch.Tensor:
     """out = epilogue(a[M,K] @ w[N,K]^T); 2-D row-contiguous bf16 views (row strides are honoured).
     ``rope`` (EPI_ROPE_QKV only) = (cos, sin, positions, q_out, k_out, group): see include/mjv.h.
     ``workspace``: split-K scratch of THIS call (default: the calling thread's ``set_gemm_workspace`` buffer);
@@ -165,7 +185,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EP
     ``padded_rows(N)``)."""
     if isinstance(a, MX8):
         assert res_mod == 0 and out_group == 0 and out_rows is None and rope is None, "MXFP8 GEMMs write plain rows"
-        return _gemm_mxfp8(a, w, out, epilogue, bias, scale, res, M, workspace, tile)
+        return _gemm_mxfp8(a, w, out, epilogue, bias, scale, res, M, workspace, tile, _plan_cus)
     _chk_bf16(a, w, out, bias, scale, res)
     lib = load_library()
     d = GemmDesc()
@@ -203,6 +223,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, epilogue: int = EP
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     d.tile = _tls.tile if tile is None else tile
     with torch.cuda.device(out.device):   # the library plans against / sets attributes on the CURRENT device
+        if _plan_cus is not None:
+            return gemm_desc_plan(d, _plan_cus)
         check(lib.mjv_gemm_bf16(C.byref(d), _stream(out)), "mjv_gemm_bf16")
     return out
 

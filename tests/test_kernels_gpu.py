@@ -849,6 +849,95 @@ def test_gemm_tail_peeling_is_invisible(cuda):
     assert torch.equal(x3, ref3)
 
 
+def _plan_cases(c):
+    """shapes built from the device's CU count c, so that they take these branches on whatever part the test runs on"""
+    return {
+        "peel_to_skinny": dict(M=256 * c + 64, N=256, K=64, epi="bias"),           # c + 1 tiles: one round + 1 -> 64 tail rows
+        "peel_to_128_tail": dict(M=256 * c + 300, N=256, K=64, epi="bias"),        # c + 2 tiles -> 300 tail rows
+        "persistent": dict(M=256 * c, N=512, K=256, epi="bias"),                   # 2 c tiles, 4 K-tiles
+        "odd_nk_one_tile_kernel": dict(M=256 * c, N=512, K=192, epi="bias"),       # 3 K-tiles: not the persistent form
+        "sliced_256": dict(M=592, N=2048, K=8192, epi="scale_res", ws=True),
+        "sliced_128": dict(M=300, N=512, K=4096, epi="bias", ws=True),
+        "rope_fallback_on_peeled_tail": dict(M=256 * (c // 2) + 300, N=512, K=64, epi="rope"),   # c + 4 tiles -> 300 tail rows
+        "mxfp8_peeled_sliced_tail": dict(M=2112, N=8192, K=1024, epi="bias", ws=True, fp8=True),
+    }
+
+
+@pytest.mark.parametrize("case", list(_plan_cases(256)))
+def test_gemm_plan_is_what_ran(cuda, case):
+    """mjv_gemm_plan against the profiler: one ``ops.gemm`` call records exactly the plan's launches - tag, count, flops share -
+    and the result is the fp32 reference's (operands in {-1, 0, 1}: every partial sum is an exactly representable integer, so
+    the result is bit-exact whichever kernels, row split and K slices the plan chose)."""
+    from mj_video_amd import ops
+    c = torch.cuda.get_device_properties(cuda).multi_processor_count
+    p = _plan_cases(c)[case]
+    M, N, K, epi, fp8 = p["M"], p["N"], p["K"], p["epi"], p.get("fp8", False)
+    g = torch.Generator().manual_seed(17)
+    a = torch.randint(-1, 2, (M, K), generator=g).float().to(BF) * (torch.rand(M, K, generator=g) < 0.15).to(BF)   # |sum| < 256
+    w = torch.randint(-1, 2, (N, K), generator=g).float().to(BF)
+    bias = None if epi == "rope" else torch.randint(-2, 3, (N,), generator=g).float().to(BF)
+    res = torch.randint(-8, 9, (M, N), generator=g).float().to(BF) if epi == "scale_res" else None
+    lin = (a.float() @ w.float().t() + (bias.float() if bias is not None else 0.0)).to(BF)
+    kw = dict(epilogue={"bias": ops.EPI_BIAS, "scale_res": ops.EPI_SCALE_RES, "rope": ops.EPI_ROPE_QKV}[epi],
+              bias=None if bias is None else bias.to(cuda), tile=0)
+    if p.get("ws"):
+        kw["workspace"] = torch.empty(ops.gemm_workspace_bytes(), dtype=torch.uint8, device=cuda)
+    if res is not None:
+        kw["res"] = res.to(cuda)
+    if epi == "rope":
+        G, D = 2, 128
+        pos = torch.randint(0, 64, (M,), generator=g).to(torch.int32)
+        inv = 1.0 / (1e6 ** (torch.arange(0, D, 2).float() / D))
+        fr = torch.einsum("i,j->ij", torch.arange(64).float(), inv)
+        emb = torch.cat((fr, fr), -1)
+        cos, sin = emb.cos().to(BF), emb.sin().to(BF)
+        q, k = torch.empty(M, G * D, dtype=BF, device=cuda), torch.empty(M, D, dtype=BF, device=cuda)
+        kw["rope"] = (cos.to(cuda), sin.to(cuda), pos.to(cuda), q, k, G)
+    A, W = a.to(cuda), w.to(cuda)
+    if fp8:
+        A, W = ops.quantize_mxfp8(A), ops.quantize_mxfp8(W)      # (-1, 0, 1 are e4m3 values: the quantised operands are exact)
+    out = torch.zeros(M, N, dtype=BF, device=cuda)
+    plan = ops.gemm_plan(A, W, out, **kw)
+    assert plan == ops.gemm_plan(A, W, out, cus=c, **kw), "cus = 0 plans against the current device"
+    ops.prof_filter(None)
+    ops.prof_reset()
+    ops.prof_enable(True)
+    try:
+        ops.gemm(A, W, out, **kw)
+        torch.cuda.synchronize()
+    finally:
+        ops.prof_enable(False)
+    tags = ops.prof_results()
+    ops.prof_reset()
+    names = ("bias", "bias_gelu", "bias_relu", "scale_res", "silu_mul", "rope_qkv")
+    want = {}
+    for L in plan["launches"]:
+        tag = "gemm{}{}{}_{}".format(L["family"], "f8" if fp8 else "", "s" if L["family"] == 256 and L["split"] > 1 else "", names[L["epilogue"]])
+        n, fl = want.get(tag, (0, 0.0))
+        want[tag] = (n + 1, fl + 2.0 * M * N * K * (L["rows"] / M))
+        if L["rope_split_after"]:
+            want["rope_split"] = (want.get("rope_split", (0, 0.0))[0] + 1, 0.0)
+    assert {t: (v["launches"], pytest.approx(v["flops"], rel=1e-12)) for t, v in tags.items()} == want, (plan, tags)
+    # the case took the branch it is named for
+    fam = [(L["family"], L["split"] > 1, L["persistent"], L["rope_split_after"]) for L in plan["launches"]]
+    assert {"peel_to_skinny": fam == [(256, False, 0, 0), (64, False, 0, 0)], "peel_to_128_tail": fam == [(256, False, 0, 0), (128, False, 0, 0)],
+            "persistent": fam == [(256, False, 1, 0)], "odd_nk_one_tile_kernel": fam == [(256, False, 0, 0)],
+            "sliced_256": fam == [(256, True, 0, 0)] or c < 48, "sliced_128": fam == [(128, True, 0, 0)] or c < 8,
+            "rope_fallback_on_peeled_tail": fam == [(256, False, 0, 0), (128, False, 0, 1)],
+            "mxfp8_peeled_sliced_tail": fam == [(256, False, 0, 0), (256, True, 0, 0)] or c != 256}[case], (c, plan)
+    if epi == "scale_res":
+        assert torch.equal(out.cpu(), (res.float() + lin.float()).to(BF))
+    elif epi == "rope":
+        t = lin.view(M, 1, G + 2, D)
+        rot = lambda x: torch.cat((-x[..., D // 2:], x[..., :D // 2]), -1)
+        cs, sn = cos[pos.long()][:, None, None, :], sin[pos.long()][:, None, None, :]
+        assert torch.equal(q.cpu(), ((t[:, :, :G] * cs) + (rot(t[:, :, :G]) * sn)).reshape(M, -1))     # bf16 ops, as test_rope_split
+        assert torch.equal(k.cpu(), ((t[:, :, G:G + 1] * cs) + (rot(t[:, :, G:G + 1]) * sn)).reshape(M, -1))
+        assert torch.equal(out.view(M, 1, G + 2, D)[:, :, G + 1].cpu(), t[:, :, G + 1]), "v goes to its own columns of C"
+    else:
+        assert torch.equal(out.cpu(), lin)
+
+
 def test_attention_long_context_c4(cuda, attn_variant):
     """BASELINE.json configs[3] shape: one causal sequence of 28 837 tokens (16 frames x 7 tiles x 256 + text), D=128 GQA.
     The eager reference would need a 28.8k x 28.8k score matrix per head; the fp32 reference here is evaluated in query
