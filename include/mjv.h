@@ -40,6 +40,9 @@
  * prefix that the captions of a video share.
  * ABI 7, additive (MJV_ABI_VERSION stays 7): mjv_gemm_plan - the launches mjv_gemm_bf16 makes for a descriptor, readable without
  * a GPU and for any number of compute units.
+ * ABI 7, additive (MJV_ABI_VERSION stays 7; mjv_attn_ctx_desc is untouched): mjv_attn_ctx_segments with mjv_attention_ctx_seg_plan /
+ * _seg_workspace_bytes / _seg_bf16 - a context of the caption pass may be the concatenation of several row ranges that live in
+ * different tensors, and contexts may share ranges (a video that grows frame by frame, one video under several instructions).
  */
 #ifndef MJV_H_
 #define MJV_H_
@@ -303,6 +306,35 @@ int64_t mjv_attention_ctx_plan(const mjv_attn_ctx_desc* d, int32_t* plan_host, i
 /* bytes of fp32 partials the launch described by `d` (index arrays and sizes only) needs; negative = MJV_E_* */
 int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d);
 int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream);
+
+/* ABI 7, additive - SEGMENTED contexts.  The three entries above are the three below with seg == NULL, int for int and bit for
+ * bit.  With segments the keys of context c are, in key order, the first use_len[u] rows of tensor use_tensor[u] for
+ * u = cu_use[c] .. cu_use[c + 1] - 1: ctx_k_list / ctx_v_list then hold one base pointer per TENSOR (n_tensors entries, every
+ * tensor with the leading dimensions / head strides of the descriptor and at least the rows its longest use reads), and two
+ * contexts may name the same tensor - a parent's rows are read where they lie by every context grown or branched from it.
+ * Checked on the host before any launch (MJV_E_ARG, the message names the use or the context):
+ *   - segments need the pointer lists: seg != NULL with packed ctx_k / ctx_v is refused (the launch entry; the plan and workspace
+ *     queries read no pointer);
+ *   - every context has at least one use, cu_use[0] == 0, cu_use[n_contexts] == n_uses;
+ *   - cu_context[c + 1] - cu_context[c] (which still gives a context's length) equals the sum of its use_len;
+ *   - ctx_any_length must be 1 unless every use_len is a multiple of 64;  use_len > 0;  0 <= use_tensor < n_tensors;
+ *   - head_dim != 128 stays MJV_E_UNSUPPORTED with the message it has.
+ * Plan: a context's key tiles are the sum over its uses of ceil(use_len / 64); the number of pieces wanted follows from the
+ * context's query count and that total as for a plain context, and every use is cut into pieces of the resulting chunk - a
+ * piece never straddles two uses, a use's last piece ends at use_len and masks the keys behind it (rows behind use_len are
+ * NEVER READ).  A tile's parts stay contiguous and in key order, then the own part: the merge is the plain one.  A part's
+ * first / end key are relative to its tensor and its fourth int is the tensor's list entry.  Where a context is cut depends on
+ * its own query count and use lengths alone.  A context of exactly one use has the plain plan of that context except for that
+ * fourth int; where the use boundaries fall on the plain plan's piece boundaries the result has the plain launch's bits. */
+typedef struct mjv_attn_ctx_segments {
+  const int32_t* cu_use;      /* HOST [n_contexts + 1]: context c = uses cu_use[c] .. cu_use[c+1]-1, in key order; >= 1 use each */
+  const int32_t* use_tensor;  /* HOST [n_uses]: entry of ctx_k_list / ctx_v_list this use reads (two contexts may name the same one) */
+  const int32_t* use_len;     /* HOST [n_uses]: the first use_len keys of that tensor, > 0; rows behind are never read */
+  int32_t n_uses, n_tensors;  /* n_tensors = entries of ctx_k_list / ctx_v_list */
+} mjv_attn_ctx_segments;
+int64_t mjv_attention_ctx_seg_plan(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, int32_t* plan_host, int64_t plan_ints);
+int64_t mjv_attention_ctx_seg_workspace_bytes(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg);
+int mjv_attention_ctx_seg_bf16(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, void* stream);
 
 /* LayerNorm over the last dim, fp32 statistics, bf16 out (nn.LayerNorm on bf16:
  * modeling_intern_vit.py:291,293; modeling_internvl_chat.py:136).

@@ -107,6 +107,13 @@ def _tail_layout(cls):
 (_ATTN_CTX_ANY_LENGTH_OFFSET,), _ATTN_CTX_DESC_BYTES = _tail_layout(AttnCtxDesc)
 
 
+class AttnCtxSegments(C.Structure):
+    """mjv_attn_ctx_segments (ABI 7, additive): HOST arrays - context c is the concatenation of the first ``use_len[u]`` rows of
+    tensor ``use_tensor[u]`` (an entry of ctx_k_list / ctx_v_list) for u in [cu_use[c], cu_use[c + 1])"""
+    _fields_ = [("cu_use", C.c_void_p), ("use_tensor", C.c_void_p), ("use_len", C.c_void_p),
+                ("n_uses", C.c_int32), ("n_tensors", C.c_int32)]
+
+
 class HeadsDesc(C.Structure):
     _fields_ = [("hr", C.c_void_p), ("hg", C.c_void_p), ("ldh", C.c_int64), ("hidden", C.c_int32),
                 ("ga", C.c_void_p), ("gc", C.c_void_p), ("ldg", C.c_int64), ("gate_hidden", C.c_int32),
@@ -132,6 +139,9 @@ SYMBOLS = {
     "mjv_attention_ctx_plan": (C.c_int64, [C.POINTER(AttnCtxDesc), _VP, _I64]),
     "mjv_attention_ctx_workspace_bytes": (C.c_int64, [C.POINTER(AttnCtxDesc)]),
     "mjv_attention_ctx_bf16": (C.c_int, [C.POINTER(AttnCtxDesc), _VP]),
+    "mjv_attention_ctx_seg_plan": (C.c_int64, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments), _VP, _I64]),
+    "mjv_attention_ctx_seg_workspace_bytes": (C.c_int64, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments)]),
+    "mjv_attention_ctx_seg_bf16": (C.c_int, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments), _VP]),
     "mjv_layernorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, _VP]),
     "mjv_rmsnorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _VP]),
     "mjv_mxfp8_scale_bytes": (C.c_int64, [_I64, _I64]),

@@ -1340,13 +1340,15 @@ struct CtxArgs {
   int n_kv, G, n_heads;
   int n_parts, n_tiles, total_q;
   float scale;
+  int seg;          // 1 = segmented launch: a context piece reads the list entry its PART names (launch-uniform)
 };
 
 // plan layout (int32): header | parts [n_parts][PART_INTS] | tiles [n_tiles][TILE_INTS] | rowq [n_tiles][TR / G] |
 // rowpos [n_tiles][TR / G] | qinfo [total_q][2]
 //   header : {format tag, n_parts, n_tiles, total_q, G, n_kv, 0, 0} - for whoever reads a plan on the host (the tests do); the
 //            kernels get these counts as arguments and never read the header
-//   part   : {tile, first key, end key, 0}
+//   part   : {tile, first key, end key, 0}; a segmented plan (mjv_attn_ctx_segments): first / end key relative to the
+//            tensor of the piece's use, and the fourth int = that tensor's entry of ctx_k_list / ctx_v_list
 //   tile   : {0 context / 1 own, first K / V row, keys (host readers only), first part, parts, stacked rows, context number
 //            (context tiles; 0 for own tiles), 0}
 MJV_DEV const int* plan_parts(const CtxArgs& p) { return p.plan + HDR; }
@@ -1375,10 +1377,12 @@ __global__ __launch_bounds__(256, 2) void attn_ctx_kernel(CtxArgs p) {
   const int key_row0 = te[1], n_rows = te[5];
   const int QS = TR / p.G;
 
-  // a context tile's rows: the packed buffer from the context's first row on, or (per-context bases) the context's own tensor
+  // a context tile's rows: the packed buffer from the context's first row on, or (per-context bases) the context's own tensor,
+  // or (segmented launch) the tensor of the use this piece lies in
   const bool listed = !own && p.Kc_list != nullptr;
-  const u16* Kcb = listed ? p.Kc_list[te[6]] : p.Kc + (long)key_row0 * p.ldkc;
-  const u16* Vcb = listed ? p.Vc_list[te[6]] : p.Vc + (long)key_row0 * p.ldvc;
+  const int entry = p.seg ? pe[3] : te[6];
+  const u16* Kcb = listed ? p.Kc_list[entry] : p.Kc + (long)key_row0 * p.ldkc;
+  const u16* Vcb = listed ? p.Vc_list[entry] : p.Vc + (long)key_row0 * p.ldvc;
   const u16* Kg = own ? p.K + (long)kvh * p.khs + (long)key_row0 * p.ldk : Kcb + (long)kvh * p.kchs;
   const u16* Vg = own ? p.V + (long)kvh * p.vhs + (long)key_row0 * p.ldv : Vcb + (long)kvh * p.vchs;
   const long ldk = own ? p.ldk : p.ldkc, ldv = own ? p.ldv : p.ldvc;
@@ -1586,8 +1590,10 @@ struct PlanInfo {
   double pairs = 0;   // (query, key) pairs per q-head
 };
 
-// Validates the index arrays (HOST) of a descriptor and lays the plan out; `out` == nullptr: sizes only.
-int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
+// Validates the index arrays (HOST) of a descriptor and lays the plan out; `out` == nullptr: sizes only.  `seg` (or nullptr):
+// every context is the concatenation of its uses' key ranges (mjv_attn_ctx_segments) - a use is cut like a context of its own
+// length with the chunk its CONTEXT's totals give, so a piece never straddles two uses.
+int ctx_plan_build(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, int32_t* out, PlanInfo* info) {
   MJV_REQUIRE(d && d->cu_seqlens && d->context_index && d->cu_context, "attention_ctx: null index array (cu_seqlens / context_index / cu_context are host arrays)");
   MJV_REQUIRE(d->n_seqs > 0 && d->n_contexts > 0 && d->n_heads > 0 && d->kv_group > 0, "attention_ctx: bad sizes");
   MJV_REQUIRE(d->n_heads % d->kv_group == 0, "attention_ctx: n_heads %% kv_group != 0");
@@ -1601,6 +1607,27 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
   MJV_REQUIRE(d->cu_seqlens[0] == 0 && (!d->cu_seqlens_q || d->cu_seqlens_q[0] == 0), "attention_ctx: cu_seqlens / cu_seqlens_q start at 0");
   MJV_REQUIRE(d->cu_context[0] >= 0, "attention_ctx: cu_context[0] < 0");
   MJV_REQUIRE(d->ctx_any_length == 0 || d->ctx_any_length == 1, "attention_ctx: ctx_any_length %d not in {0, 1}", d->ctx_any_length);
+  if (seg) {
+    MJV_REQUIRE(seg->cu_use && seg->use_tensor && seg->use_len, "attention_ctx: null segment array (cu_use / use_tensor / use_len are host arrays)");
+    MJV_REQUIRE(seg->n_uses > 0 && seg->n_tensors > 0, "attention_ctx: segments with %d uses of %d tensors", seg->n_uses, seg->n_tensors);
+    MJV_REQUIRE(seg->cu_use[0] == 0 && seg->cu_use[d->n_contexts] == seg->n_uses,
+                "attention_ctx: cu_use runs from %d to %d, the segments hold uses 0 .. %d", seg->cu_use[0], seg->cu_use[d->n_contexts], seg->n_uses);
+    for (int c = 0; c < d->n_contexts; ++c)
+      MJV_REQUIRE(seg->cu_use[c + 1] > seg->cu_use[c], "attention_ctx: context %d has no use (cu_use %d .. %d)", c, seg->cu_use[c], seg->cu_use[c + 1]);
+    for (int u = 0; u < seg->n_uses; ++u) {
+      MJV_REQUIRE(seg->use_tensor[u] >= 0 && seg->use_tensor[u] < seg->n_tensors, "attention_ctx: use %d names tensor %d of %d", u,
+                  seg->use_tensor[u], seg->n_tensors);
+      MJV_REQUIRE(seg->use_len[u] > 0, "attention_ctx: use %d has %d keys - a positive length is required", u, seg->use_len[u]);
+      MJV_REQUIRE(d->ctx_any_length || seg->use_len[u] % KB == 0,
+                  "attention_ctx: use %d has %d keys - ctx_any_length must be 1 unless every use is a multiple of %d", u, seg->use_len[u], KB);
+    }
+    for (int c = 0; c < d->n_contexts; ++c) {
+      long sum = 0;
+      for (int u = seg->cu_use[c]; u < seg->cu_use[c + 1]; ++u) sum += seg->use_len[u];
+      MJV_REQUIRE(sum == (long)d->cu_context[c + 1] - d->cu_context[c], "attention_ctx: context %d has %ld keys, its uses add up to %ld", c,
+                  (long)d->cu_context[c + 1] - d->cu_context[c], sum);
+    }
+  }
   for (int c = 0; c < d->n_contexts; ++c) {
     const long len = (long)d->cu_context[c + 1] - d->cu_context[c];
     if (d->ctx_any_length) MJV_REQUIRE(len > 0, "attention_ctx: context %d has %ld keys - a positive length is required", c, len);
@@ -1633,7 +1660,11 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
   for (int c = 0; c < d->n_contexts; ++c) {
     if (!ctx_q[c]) continue;
     const long tiles = (ctx_q[c] + QS - 1) / QS;
-    const int kt = (d->cu_context[c + 1] - d->cu_context[c] + KB - 1) / KB;   // key tiles; the last may be ragged (ctx_any_length)
+    int kt = (d->cu_context[c + 1] - d->cu_context[c] + KB - 1) / KB;   // key tiles; the last may be ragged (ctx_any_length)
+    if (seg) {                                                           // ... the last of every use
+      kt = 0;
+      for (int u = seg->cu_use[c]; u < seg->cu_use[c + 1]; ++u) kt += (seg->use_len[u] + KB - 1) / KB;
+    }
     // where a context is cut depends on ITS tiles and length alone; pieces of at least two key tiles, whole tiles except the
     // context's last piece, which ends at the context's length
     long want = (TARGET_WG + tiles * n_kv - 1) / (tiles * n_kv);
@@ -1641,6 +1672,10 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
     const int chunk_t = (int)((kt + want - 1) / want);
     ctx_chunk[c] = chunk_t * KB;
     ctx_split[c] = (kt + chunk_t - 1) / chunk_t;
+    if (seg) {   // every use is cut on its own: its last piece ends at use_len
+      ctx_split[c] = 0;
+      for (int u = seg->cu_use[c]; u < seg->cu_use[c + 1]; ++u) ctx_split[c] += ((seg->use_len[u] + KB - 1) / KB + chunk_t - 1) / chunk_t;
+    }
     n_ctx_tiles += tiles;
     n_parts += tiles * ctx_split[c];
   }
@@ -1670,6 +1705,14 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
       int32_t* te = tiles + t * TILE_INTS;
       te[0] = 0; te[1] = d->cu_context[c]; te[2] = clen; te[3] = (int32_t)pt; te[4] = ctx_split[c];
       te[5] = (int32_t)(std::min((long)QS, ctx_q[c] - i * QS) * G); te[6] = c; te[7] = 0;
+      if (seg) {   // the uses in key order, each from its tensor's row 0: keys relative to that tensor, its list entry in [3]
+        for (int u = seg->cu_use[c]; u < seg->cu_use[c + 1]; ++u)
+          for (int k0 = 0; k0 < seg->use_len[u]; k0 += ctx_chunk[c], ++pt) {
+            int32_t* pe = parts + pt * PART_INTS;
+            pe[0] = (int32_t)t; pe[1] = k0; pe[2] = std::min(seg->use_len[u], k0 + ctx_chunk[c]); pe[3] = seg->use_tensor[u];
+          }
+        continue;
+      }
       for (int s = 0; s < ctx_split[c]; ++s, ++pt) {
         int32_t* pe = parts + pt * PART_INTS;
         pe[0] = (int32_t)t; pe[1] = s * ctx_chunk[c]; pe[2] = std::min(clen, (s + 1) * ctx_chunk[c]); pe[3] = 0;
@@ -1710,29 +1753,31 @@ int ctx_plan_build(const mjv_attn_ctx_desc* d, int32_t* out, PlanInfo* info) {
 }  // namespace cx
 }  // namespace
 
-extern "C" int64_t mjv_attention_ctx_plan(const mjv_attn_ctx_desc* d, int32_t* plan_host, int64_t plan_ints) {
+extern "C" int64_t mjv_attention_ctx_seg_plan(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, int32_t* plan_host,
+                                              int64_t plan_ints) {
   cx::PlanInfo info;
-  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  const int rc = cx::ctx_plan_build(d, seg, nullptr, &info);
   if (rc != MJV_OK) return rc;
   if (!plan_host) return info.ints;
   if (plan_ints < info.ints) {
     mjv_set_error("attention_ctx_plan: the plan needs %ld ints, the buffer holds %ld", (long)info.ints, (long)plan_ints);
     return MJV_E_ARG;
   }
-  const int rc2 = cx::ctx_plan_build(d, plan_host, &info);
+  const int rc2 = cx::ctx_plan_build(d, seg, plan_host, &info);
   return rc2 != MJV_OK ? rc2 : info.ints;
 }
 
-extern "C" int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d) {
+extern "C" int64_t mjv_attention_ctx_seg_workspace_bytes(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg) {
   cx::PlanInfo info;
-  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  const int rc = cx::ctx_plan_build(d, seg, nullptr, &info);
   return rc != MJV_OK ? rc : info.ws_bytes;
 }
 
-extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) {
+extern "C" int mjv_attention_ctx_seg_bf16(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, void* stream) {
   MJV_REQUIRE(d && d->Q && d->K && d->V && d->O, "attention_ctx: null pointer");
   MJV_REQUIRE(!d->ctx_k_list == !d->ctx_v_list, "attention_ctx: ctx_k_list and ctx_v_list must both be given, or neither");
   const bool listed = d->ctx_k_list != nullptr;
+  MJV_REQUIRE(!seg || listed, "attention_ctx: segments need the pointer lists ctx_k_list / ctx_v_list (packed ctx_k / ctx_v hold one run of rows per context)");
   MJV_REQUIRE(listed || (d->ctx_k && d->ctx_v), "attention_ctx: null pointer (ctx_k / ctx_v, or ctx_k_list / ctx_v_list)");
   if (!d->causal) {
     mjv_set_error("attention_ctx: only causal launches are built (a sequence's own rows follow its context)");
@@ -1740,7 +1785,7 @@ extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) 
   }
   MJV_REQUIRE(d->score_round_mode == 1 || d->score_round_mode == 2, "attention_ctx: score_round_mode %d not in {1, 2}", d->score_round_mode);
   cx::PlanInfo info;
-  const int rc = cx::ctx_plan_build(d, nullptr, &info);
+  const int rc = cx::ctx_plan_build(d, seg, nullptr, &info);
   if (rc != MJV_OK) return rc;
   MJV_REQUIRE(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 8 == 0 && d->ld_ctx_k % 8 == 0 && d->ld_ctx_v % 8 == 0,
               "attention_ctx: ld alignment (multiples of 8 elements)");
@@ -1766,6 +1811,7 @@ extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) 
   a.G = d->kv_group; a.n_heads = d->n_heads; a.n_kv = d->n_heads / d->kv_group;
   a.n_parts = (int)info.n_parts; a.n_tiles = (int)info.n_tiles; a.total_q = (int)info.total_q;
   a.scale = d->scale;
+  a.seg = seg != nullptr;
   const long slabs = info.n_parts * a.n_kv;
   a.ws_ml = (float*)d->workspace;
   a.ws_acc = (float*)d->workspace + slabs * cx::TR * 2;
@@ -1779,3 +1825,10 @@ extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) 
   hipLaunchKernelGGL((cx::attn_ctx_combine_kernel<128>), dim3((unsigned)((pairs + 7) / 8)), dim3(256), 0, s, a);
   return mjv_check_launch("attention_ctx combine");
 }
+
+// the three entries of before: the segmented ones with no segments
+extern "C" int64_t mjv_attention_ctx_plan(const mjv_attn_ctx_desc* d, int32_t* plan_host, int64_t plan_ints) {
+  return mjv_attention_ctx_seg_plan(d, nullptr, plan_host, plan_ints);
+}
+extern "C" int64_t mjv_attention_ctx_workspace_bytes(const mjv_attn_ctx_desc* d) { return mjv_attention_ctx_seg_workspace_bytes(d, nullptr); }
+extern "C" int mjv_attention_ctx_bf16(const mjv_attn_ctx_desc* d, void* stream) { return mjv_attention_ctx_seg_bf16(d, nullptr, stream); }

@@ -249,6 +249,46 @@ def score_caption_matrix(model, config, tokenizer, videos: Sequence[torch.Tensor
     return torch.cat(out).view(V, M, -1)
 
 
+@torch.no_grad()
+def score_growing_video(model, config, tokenizer, pixels: torch.Tensor, captions: Sequence[str], generation_config: dict,
+                        lengths: Sequence[int] = (2, 4, 8)) -> torch.Tensor:
+    """ONE video ([F, 3, S, S], a tile per frame) scored under M captions at several lengths - its first ``lengths[0]`` frames,
+    its first ``lengths[1]`` ... (ascending, <= F): dense / temporal reward, a clip that is still being generated.  The first
+    length is encoded (``model.encode_video``), every further one EXTENDS the context before it (``model.extend_context``): the
+    vision tower and the context pass run over each frame once, whatever the number of lengths, and no cached row is copied.
+    The prompt of L frames is ``video_prefix(L) + caption`` - its image tokens are one run, so the prompt of a shorter length
+    is a prefix of the longer one's up to the end of its own image run, and that column is where each context ends
+    (``context_len``; ``caption_attention`` "shared" scores contexts of any length and segmented ones).
+    Returns ``[len(lengths), M, 1 + n_aspects + n_objectives]`` fp32: row [i, j] = what ``model.forward`` gives for the first
+    ``lengths[i]`` frames under caption j, up to fp32 summation order."""
+    _lib.assert_product_library()
+    dev = model.model.device
+    pad_id = model.config.pad_token_id
+    if pad_id is None:
+        raise ValueError("model.config.pad_token_id must be set to batch captions (eval_genai_mjvideo.py:112)")
+    lengths = [int(n) for n in lengths]
+    if not lengths or not captions:
+        raise ValueError("score_growing_video needs at least one length and one caption")
+    if lengths[0] < 1 or any(b <= a for a, b in zip(lengths, lengths[1:])) or lengths[-1] > int(pixels.shape[0]):
+        raise ValueError(f"lengths {lengths} must ascend strictly within [1, {int(pixels.shape[0])}] (the video's frames)")
+    ctx_id = model.model.img_context_token_id
+    pixels = pixels.to(torch.bfloat16)
+    out, ctx, done = [], None, 0
+    for n in lengths:
+        pv = pixels[:n]
+        rows = [prepare_chat_input(config, tokenizer, pv, video_prefix(n) + c, generation_config, device="cpu")[0] for c in captions]
+        end = int(np.flatnonzero(rows[0].reshape(-1).numpy() == ctx_id)[-1]) + 1
+        if ctx is None:
+            ctx = model.encode_video(pv.to(dev), rows[0], context_len=end)
+        else:
+            ctx = model.extend_context(ctx, rows[0], pixels[done:n].to(dev), context_len=end)
+        done = n
+        ids_b, mask = pad_right(rows, pad_id)
+        model.score_captions(ctx, ids_b.to(dev), mask.to(dev))
+        out.append(model.last_packed34)
+    return torch.stack(out)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Collator batch format and MJ-BENCH-VIDEO label schema (SURVEY.md §8(f) items 2-3)
 @torch.no_grad()

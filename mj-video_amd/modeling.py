@@ -101,34 +101,59 @@ class VideoContext:
     numerics, FFN format, norm fusion, device): ``score_captions`` refuses it under any other and never rebuilds it.
     A context of ``model.encode_videos`` is a VIEW: ``k[layer]`` / ``v[layer]`` / ``img_tail`` are row ranges of buffers the call's
     videos share, which stay alive as long as any of its contexts does (``storage_nbytes``: what this context keeps alive;
-    ``nbytes``: its own rows).  ``clone()`` gives a context that owns its rows."""
+    ``nbytes``: its own rows).  ``clone()`` gives a context that owns its rows.
+    A context of ``model.extend_context`` is SEGMENTED: it holds the segments of the context it grew or branched from by
+    reference and the rows of its own new tokens (``segments``; ``k`` / ``v``: the own, newest segment; ``P``: the total)."""
 
-    def __init__(self, ids, P, k, v, img_tail, tail_cols, n_img, settings, ready, stream, device):
+    def __init__(self, ids, P, k, v, img_tail, tail_cols, n_img, settings, ready, stream, device, base=()):
         self.ids, self.P, self.k, self.v, self.img_tail, self.tail_cols, self.n_img = ids, P, k, v, img_tail, tail_cols, n_img
         self.settings, self.ready, self.stream, self.device = settings, ready, stream, device
+        # a context of ``extend_context``: the segments of its ancestors (k-list, v-list, length), in key order, held BY
+        # REFERENCE - ``k`` / ``v`` are then its own newest segment, the rows of tokens [P - own length, P)
+        self._base = list(base)
+
+    @property
+    def segments(self):
+        """[(k-list, v-list, length)] in key order: the keys / values of tokens [0, P) are the concatenation of the segments'
+        rows, layer by layer.  One entry for a context of ``encode_video`` / ``encode_videos``; a context of
+        ``extend_context`` holds its ancestors' entries (the same list objects: no row is copied) and its own last"""
+        return self._base + [(self.k, self.v, self.P - sum(n for _, _, n in self._base))]
 
     @property
     def nbytes(self) -> int:
+        """bytes of this context's OWN rows (its newest segment) and ``img_tail``"""
         return sum(t.numel() * t.element_size() for t in self.tensors())
 
     @property
     def storage_nbytes(self) -> int:
         """bytes of device memory this context keeps alive: every distinct storage behind its tensors, whole (= ``nbytes`` for a
-        context that owns its rows; for a view of ``encode_videos``, the buffers of all the call's videos)"""
-        return sum({s.data_ptr(): s.nbytes() for s in (t.untyped_storage() for t in self.tensors())}.values())
+        context that owns its rows; for a view of ``encode_videos``, the buffers of all the call's videos; for a context of
+        ``extend_context``, its ancestors' segments too)"""
+        return sum({s.data_ptr(): s.nbytes() for s in (t.untyped_storage() for t in self.all_tensors())}.values())
 
     def tensors(self):
         return self.k + self.v + [self.img_tail]
 
+    def all_tensors(self):
+        """``tensors()`` and the rows of every ancestor's segment: all a scoring pass reads"""
+        return [t for k, v, _ in self._base for t in k + v] + self.tensors()
+
     def clone(self) -> "VideoContext":
         """an owning copy (same rows, same settings), made on the current stream of the context's device: dropping the other
-        contexts of an ``encode_videos`` call then frees their rows"""
+        contexts of an ``encode_videos`` call then frees their rows.  The clone of a segmented context is PLAIN: its segments'
+        rows copied into one contiguous run per layer (what ``caption_attention`` "per-context" takes)"""
         ready, stream = self.ready, self.stream
         if self.device.type == "cuda":
             cur = torch.cuda.current_stream(self.device)
             if stream != cur.cuda_stream:
                 cur.wait_event(ready)
-        k, v, img_tail = [t.clone() for t in self.k], [t.clone() for t in self.v], self.img_tail.clone()
+        if self._base:
+            segs = self.segments
+            k = [torch.cat([sk[li] for sk, _, _ in segs]) for li in range(len(self.k))]
+            v = [torch.cat([sv[li] for _, sv, _ in segs]) for li in range(len(self.v))]
+            img_tail = self.img_tail.clone()
+        else:
+            k, v, img_tail = [t.clone() for t in self.k], [t.clone() for t in self.v], self.img_tail.clone()
         if self.device.type == "cuda":
             ready = torch.cuda.Event()
             ready.record(cur)
@@ -1208,36 +1233,57 @@ class InternVLChatRewardModeling(nn.Module):
 
         return attend
 
-    def _attend_contexts_shared(self, ctxs, info, trim: bool, dev):
+    def _attend_contexts_shared(self, ctxs, info, trim: bool, dev, segmented: Optional[bool] = None):
         """Strategy of ``score_captions`` (``caption_attention`` "shared"): one mjv_attention_ctx_bf16 launch per layer for every
         context of the batch.  More than one context (``caption_context_rows``): "in-place" - ONE [layers, 2, contexts] table of
         the contexts' first-row addresses, uploaded once per call, every layer's launch handed its row; "packed" - the contexts'
-        rows gathered into one buffer per layer."""
+        rows gathered into one buffer per layer.  A context of ``extend_context`` among them (``segmented``; None: decided
+        here): "in-place" - the segmented launch (mjv_attention_ctx_seg_bf16) over a table of the SEGMENT tensors, a segment
+        that several contexts hold listed once; "packed" - every context's segments gathered into the packed buffer, the plain
+        launch.  ``extend_context`` itself asks for the segmented launch whatever the context is made of."""
         H, KV, G, hd, scale, mode = self._llm_geom()
         cu_ctx = np.concatenate([[0], np.cumsum([c.P for c in ctxs])]).astype(np.int32)
-        ragged = any(c.P % 64 for c in ctxs)   # a context that ends inside a key tile (encode_video's ``context_len``)
-        plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, any_length=ragged)
-        plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"],
-                                    any_length=ragged) if trim else None
+        multi = any(len(c.segments) > 1 for c in ctxs)
+        if segmented is None:
+            segmented = multi and self.caption_context_rows == "in-place"
+        segs = [c.segments for c in ctxs]
+        uses, tensors = None, []
+        if segmented:
+            entry = {}
+            for sg in segs:
+                for kl, vl, _ in sg:
+                    if id(kl) not in entry:
+                        entry[id(kl)] = len(tensors)
+                        tensors.append((kl, vl))
+            uses = [[(entry[id(kl)], n) for kl, _, n in sg] for sg in segs]
+            ragged = any(n % 64 for sg in uses for _, n in sg)
+        else:
+            ragged = any(c.P % 64 for c in ctxs)   # a context that ends inside a key tile (encode_video's ``context_len``)
+        kw = dict(any_length=ragged, segments=uses, n_tensors=len(tensors) if segmented else None)
+        plan_all = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, **kw)
+        plan_tail = ops.AttnCtxPlan(info["cu"], info["index"], cu_ctx, H, G, hd, dev, cu_seqlens_q=info["cu_tail"], **kw) if trim else None
         ws = self._buf("attn_ctx_ws", 1, max(plan_all.workspace_bytes, plan_tail.workspace_bytes if trim else 0), dev,
                        dtype=torch.uint8).view(-1)
         P_all, C, L = int(cu_ctx[-1]), len(ctxs), len(ctxs[0].k)
-        in_place = C > 1 and self.caption_context_rows == "in-place"
+        if not segmented:
+            tensors = [(c.k, c.v) for c in ctxs]
+        T = len(tensors)
+        in_place = segmented or (C > 1 and not multi and self.caption_context_rows == "in-place")
         if in_place:
-            table = self._buf("cap_ctx_ptrs", L, 2 * C, dev, dtype=torch.int64)
-            table.copy_(torch.from_numpy(np.stack([ops.ctx_pointer_rows([c.k[li] for c in ctxs], [c.v[li] for c in ctxs])
-                                                   for li in range(L)]).reshape(L, 2 * C)))
+            table = self._buf("cap_ctx_ptrs", L, 2 * T, dev, dtype=torch.int64)
+            table.copy_(torch.from_numpy(np.stack([ops.ctx_pointer_rows([kl[li] for kl, _ in tensors], [vl[li] for _, vl in tensors])
+                                                   for li in range(L)]).reshape(L, 2 * T)))
 
         def attend(li, q, k, v, v_head_stride, out, tail):
             ptrs = None
-            if C == 1:
+            if in_place:
+                ck, cv, ptrs = [kl[li] for kl, _ in tensors], [vl[li] for _, vl in tensors], table[li].view(2, T)
+            elif C == 1 and not multi:
                 ck, cv = ctxs[0].k[li], ctxs[0].v[li]
-            elif in_place:
-                ck, cv, ptrs = [c.k[li] for c in ctxs], [c.v[li] for c in ctxs], table[li].view(2, C)
-            else:   # one packed buffer per operand: gathered per layer
+            else:   # one packed buffer per operand: gathered per layer, segment by segment
                 ck, cv = self._buf("cap_ctx_k", P_all, KV * hd, dev), self._buf("cap_ctx_v", P_all, KV * hd, dev)
-                torch.cat([c.k[li] for c in ctxs], out=ck)
-                torch.cat([c.v[li] for c in ctxs], out=cv)
+                torch.cat([kl[li] for sg in segs for kl, _, _ in sg], out=ck)
+                torch.cat([vl[li] for sg in segs for _, vl, _ in sg], out=cv)
             ops.attention_ctx(q, k, v, out, ck, cv, plan_tail if tail else plan_all, scale, mode, ws, v_head_stride=v_head_stride,
                               ctx_list=ptrs)
 
@@ -1690,6 +1736,125 @@ class InternVLChatRewardModeling(nn.Module):
             stream = torch.cuda.current_stream(dev).cuda_stream
         return VideoContext(ids, P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
 
+    def _analyse_extension(self, ctx: VideoContext, input_ids, pixel_values=None, attention_mask=None,
+                           context_len: Optional[int] = None):
+        """The checks of ``extend_context`` (nothing is repaired) and what its pass needs: the new context's length K, the ids
+        of the new tokens [ctx.P, K), and for every new row the row of [parent's ``img_tail`` | new tiles' projections] that
+        is spliced into it (-1: a text token).  Host code: reads shapes, dtypes and the ids."""
+        if not isinstance(ctx, VideoContext):
+            raise ValueError("extend_context: the first argument is the VideoContext to extend (model.encode_video)")
+        tiles = 0
+        if pixel_values is not None:
+            if pixel_values.dim() != 4:
+                raise ValueError(f"wrong pixel_values size: {tuple(pixel_values.shape)}")
+            if pixel_values.dtype != BF16:
+                raise TypeError(f"pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
+            tiles = int(pixel_values.shape[0])
+            if not tiles:
+                raise ValueError("pixel_values holds no tile: pass None for a pure text extension")
+        ids = input_ids.detach().to("cpu").numpy()
+        if ids.ndim == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.ndim != 1:
+            raise ValueError(f"ONE prompt ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
+        N, P0 = int(ids.shape[0]), ctx.P
+        if N <= P0:
+            raise ValueError(f"the prompt has {N} tokens, the context to extend holds {P0}: nothing to add")
+        differ = np.flatnonzero(ids[:P0] != ctx.ids)
+        if differ.size:
+            raise ValueError(f"the prompt's first {P0} token ids differ from those of the context to extend "
+                             f"(first at column {int(differ[0])})")
+        cols = np.flatnonzero(ids == self.model.img_context_token_id)
+        n_new = tiles * self.model.num_image_token
+        if cols.size != ctx.n_img + n_new:
+            raise ValueError(f"{cols.size} <IMG_CONTEXT> tokens in input_ids, but the context was built from {ctx.n_img} and "
+                             f"pixel_values holds {tiles} new tiles x {self.model.num_image_token} image tokens")
+        if context_len is None:
+            K = ((int(cols[-1]) + 1) // 64) * 64 if cols.size else 0
+        else:
+            if isinstance(context_len, bool) or not isinstance(context_len, (int, np.integer)) or not 1 <= context_len <= N - 1:
+                raise ValueError(f"context_len must be None or an int in [1, {N - 1}] (the prompt has {N} tokens), "
+                                 f"got {context_len!r}")
+            K = int(context_len)
+        if K <= P0:
+            raise ValueError(f"the extended context would hold {K} tokens, the context to extend holds {P0} already: "
+                             "context_len must be greater")
+        if attention_mask is not None:
+            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
+            if am.shape[0] != N:
+                raise ValueError(f"attention_mask of {am.shape[0]} columns, the prompt has {N}")
+            if not am[:K].all():
+                raise ValueError(f"masked column {int(np.flatnonzero(~am[:K])[0])} inside the context ({K} tokens): "
+                                 "attention_mask must be set on every context column")
+        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
+        if int(ids[P0:K].min()) < 0 or int(ids[P0:K].max()) >= vocab:
+            raise IndexError(f"token id out of range [0, {vocab})")
+        # image token j of the prompt (in column order) carries embedding j of the video: j < n_in0 lie inside the parent,
+        # n_in0 <= j < ctx.n_img are the parent's img_tail, the rest the new tiles' tokens
+        n_in0, n_in = ctx.n_img - int(ctx.tail_cols.size), int((cols < K).sum())
+        if int((cols < P0).sum()) != n_in0:
+            raise ValueError("the context to extend does not match its own image-token count")   # (cannot happen: ids agree)
+        src = np.full(K - P0, -1, dtype=np.int32)
+        src[cols[n_in0:n_in] - P0] = np.arange(n_in - n_in0)
+        return dict(ids=ids[:K].copy(), new_ids=ids[P0:K].astype(np.int32), N=N, K=K, tiles=tiles, n_new=n_new, cols=cols,
+                    n_in0=n_in0, n_in=n_in, src=src)
+
+    @torch.no_grad()
+    def extend_context(self, ctx: VideoContext, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor] = None,
+                       attention_mask: Optional[torch.Tensor] = None, context_len: Optional[int] = None) -> VideoContext:
+        """A context that GROWS or BRANCHES from ``ctx`` without copying a row of it.  ``input_ids``: one full prompt whose
+        first ``ctx.P`` ids are the parent's (``ValueError`` naming the first differing column otherwise); the new context
+        covers its first K tokens, K by ``encode_video``'s rule on THIS prompt (the column after the last <IMG_CONTEXT>, cut
+        down to a multiple of 64; or ``context_len``), K > ctx.P.  Only tokens [ctx.P, K) go through the language tower:
+        positions from ctx.P, the prompt's rotary width, their attention = the own causal part over the parent's segments
+        (mjv_attention_ctx_seg_bf16), every new row's keys / values kept.  Image tokens among them take the parent's
+        ``img_tail`` first, then the projections of ``pixel_values`` - the tiles of the NEW frames only, the vision tower runs
+        on those alone; the prompt must hold ctx.n_img + new tiles x tokens per tile <IMG_CONTEXT> tokens.
+        ``pixel_values`` None: a pure text extension (one video under another instruction); no vision kernel is launched.
+        The child holds the parent's segments by reference (``VideoContext.segments``) and keeps their tensors alive; the
+        parent object may be dropped, and many children may share one parent.  The model's settings for this prompt must be
+        those the parent was built under (``ValueError``; nothing is rebuilt)."""
+        dev = self.model.device
+        self._caption_guard(dev)
+        a = self._analyse_extension(ctx, input_ids, pixel_values, attention_mask, context_len)
+        N, K, P0, cols, n_in0, n_in = a["N"], a["K"], ctx.P, a["cols"], a["n_in0"], a["n_in"]
+        if ctx.device != dev:
+            raise ValueError(f"the context to extend lives on {ctx.device}, the model on {dev}")
+        d = self._prepare(dev)
+        settings = self._cache_settings(N, dev)
+        if ctx.settings != settings:
+            raise ValueError("the context to extend was built under other settings than the model has for this prompt (weights, "
+                             "rotary base, attention_scores, FFN format or device changed since encode_video): encode the "
+                             "video again")
+        lc = self.config.llm_config
+        hdim, n = lc.hidden_size, K - P0
+        with self._gemm_scratch(dev, "g0"):
+            self._wait_for_rows(dev, ctx.stream, ctx.ready, ctx.all_tensors())
+            # embeddings of the image tokens behind the parent's P: [parent's img_tail | the new tiles' projections]
+            emb = ctx.img_tail
+            if pixel_values is not None:
+                ph, _ = self._vision_tower_launch(d, pixel_values.to(dev).contiguous())
+                mlp1 = self.model.mlp1
+                emb = torch.empty(ctx.img_tail.shape[0] + a["n_new"], hdim, dtype=BF16, device=dev)
+                emb[:ctx.img_tail.shape[0]].copy_(ctx.img_tail)
+                ops.gemm(ph[:a["n_new"]], mlp1[3].weight, emb[ctx.img_tail.shape[0]:], EPI_BIAS, bias=mlp1[3].bias)
+            x = self._buf("llm_x", n, hdim, dev)
+            ops.embed_gather(_up_pinned(a["new_ids"], dev), self.model.language_model.model.tok_embeddings.weight, x,
+                             self.model.img_context_token_id)
+            if n_in > n_in0:
+                ops.embed_gather(_up_pinned(a["src"], dev), emb, x, -1)
+            img_tail = emb[n_in - n_in0:].clone()
+            pos = torch.arange(P0, K, dtype=torch.int32, device=dev)
+            info = dict(cu=np.asarray([0, n], dtype=np.int32), index=np.zeros(1, dtype=np.int32))
+            attend = self._attend_contexts_shared([ctx], info, False, dev, segmented=True)
+            store = _Snapshot(n, [], [], compact_values=True)
+            self._language_tower(d, x, None, pos, 0, None, padded_len=N, snapshot=store, attend=attend)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(dev))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        return VideoContext(a["ids"], K, store.k, store.v, img_tail, cols[n_in:].copy(), int(cols.size), settings, ready, stream, dev,
+                            base=ctx.segments)
+
     def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = "", context_len: Optional[int] = None):
         """The checks of ``encode_video`` / ``encode_videos`` on ONE video and its prompt ([N] or [1, N]; nothing is repaired), and
         what the context pass needs of them: the first P ids, P (the column after the last <IMG_CONTEXT>, cut down to a multiple
@@ -1911,6 +2076,10 @@ class InternVLChatRewardModeling(nn.Module):
             raise ValueError(f"input_ids must be [captions, seq], got {tuple(input_ids.shape)}")
         if self.caption_attention == "per-context":   # mjv_attention_bf16's prefix rule; the shared launch takes any length
             for c, ctx in enumerate(ctxs):
+                if len(ctx.segments) > 1:
+                    raise ValueError(f"context {c} is segmented ({len(ctx.segments)} segments, model.extend_context): "
+                                     "caption_attention 'per-context' reads one contiguous run of rows per context; score "
+                                     "context.clone(), or use 'shared'")
                 if ctx.P % 64:
                     raise ValueError(f"context {c} holds {ctx.P} tokens: caption_attention 'per-context' needs a context length "
                                      "that is a multiple of 64 (prefix_len % 64 == 0); use 'shared' for a context of any length")
@@ -1940,7 +2109,7 @@ class InternVLChatRewardModeling(nn.Module):
         shared, trim = self.caption_attention == "shared", bool(self.trim_last_layer)
         with self._gemm_scratch(dev, "g0"):
             for ctx in ctxs:
-                self._wait_for_rows(dev, ctx.stream, ctx.ready, ctx.tensors())
+                self._wait_for_rows(dev, ctx.stream, ctx.ready, ctx.all_tensors())
             hidden = self._buf("llm_x", info["total"], lc.hidden_size, dev)
             ops.embed_gather(_up(info["ids"], dev), self.model.language_model.model.tok_embeddings.weight, hidden,
                              self.model.img_context_token_id)

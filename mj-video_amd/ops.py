@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_ROPE_QKV, EPI_SCALE_RES, EPI_SILU_MUL, FMT_MXFP8, AttnCtxDesc,
+from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_ROPE_QKV, EPI_SCALE_RES, EPI_SILU_MUL, FMT_MXFP8, AttnCtxDesc, AttnCtxSegments,
                    AttnDesc, GemmDesc, HeadsDesc, check, load_library)
 
 BF16 = torch.bfloat16
@@ -286,11 +286,24 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
 class AttnCtxPlan:
     """What one batch of the caption pass needs for ``attention_ctx`` (include/mjv.h, mjv_attn_ctx_desc): the HOST index arrays
     (kept alive here: the C entry reads them in every call), the device copy of the plan ``mjv_attention_ctx_plan`` derived from
-    them, and the size of the fp32 partials.  Built once per batch, used by every layer's launch."""
+    them, and the size of the fp32 partials.  Built once per batch, used by every layer's launch.
+    ``segments`` (mjv_attn_ctx_segments; None = plain contexts): one sequence per context of its uses in key order, a use =
+    (entry of the launch's tensor list, the number of that tensor's first rows it reads); ``n_tensors``: entries of the tensor
+    list (default: the largest entry named + 1).  ``cu_context`` still gives every context's total."""
 
     def __init__(self, cu_seqlens, context_index, cu_context, n_heads: int, kv_group: int, head_dim: int, device,
-                 cu_seqlens_q=None, any_length: bool = False):
+                 cu_seqlens_q=None, any_length: bool = False, segments=None, n_tensors: Optional[int] = None):
         import numpy as np
+        self.segmented = segments is not None
+        if self.segmented:
+            uses = [[(int(t), int(n)) for t, n in ctx] for ctx in segments]
+            flat = [u for ctx in uses for u in ctx]
+            self.cu_use = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(ctx) for ctx in uses])]), dtype=np.int32)
+            self.use_tensor = np.ascontiguousarray([u[0] for u in flat], dtype=np.int32)
+            self.use_len = np.ascontiguousarray([u[1] for u in flat], dtype=np.int32)
+            self.n_tensors = int(n_tensors) if n_tensors is not None else (int(self.use_tensor.max()) + 1 if flat else 0)
+            if len(uses) != len(cu_context) - 1:
+                raise ValueError(f"attention_ctx plan: segments for {len(uses)} contexts, cu_context describes {len(cu_context) - 1}")
         self.any_length = bool(any_length)   # contexts of any positive length (mjv_attn_ctx_desc.ctx_any_length); False: multiples of 64
         as_i32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32))  # noqa: E731
         self.cu, self.cu_q, self.index, self.cu_ctx = as_i32(cu_seqlens), as_i32(cu_seqlens_q), as_i32(context_index), as_i32(cu_context)
@@ -299,14 +312,14 @@ class AttnCtxPlan:
             raise ValueError("attention_ctx plan: cu_seqlens [n + 1], context_index [n], cu_context [contexts + 1], cu_seqlens_q [n + 1] or None")
         self.n_heads, self.kv_group, self.head_dim, self.device = n_heads, kv_group, head_dim, torch.device(device)
         lib = load_library()
-        d = self.desc()
-        n = lib.mjv_attention_ctx_plan(C.byref(d), None, 0)
+        d, sg = self.desc(), self.seg_desc()
+        n = lib.mjv_attention_ctx_seg_plan(C.byref(d), sg, None, 0)
         if n < 0:
             check(int(n), "mjv_attention_ctx_plan")
         host = np.empty(int(n), dtype=np.int32)
-        check(min(0, int(lib.mjv_attention_ctx_plan(C.byref(d), host.ctypes.data, int(n)))), "mjv_attention_ctx_plan")
+        check(min(0, int(lib.mjv_attention_ctx_seg_plan(C.byref(d), sg, host.ctypes.data, int(n)))), "mjv_attention_ctx_plan")
         self.plan_ints = int(n)
-        self.workspace_bytes = int(lib.mjv_attention_ctx_workspace_bytes(C.byref(d)))
+        self.workspace_bytes = int(lib.mjv_attention_ctx_seg_workspace_bytes(C.byref(d), sg))
         self.total_q = int((self.cu_q if self.cu_q is not None else self.cu)[-1])
         self.plan = torch.from_numpy(host).to(self.device, non_blocking=False)
 
@@ -319,22 +332,37 @@ class AttnCtxPlan:
         d.ctx_any_length = int(self.any_length)
         return d
 
+    def seg_desc(self):
+        """the plan's mjv_attn_ctx_segments (its arrays are kept alive here), or None for plain contexts"""
+        if not self.segmented:
+            return None
+        sg = AttnCtxSegments()
+        sg.cu_use, sg.use_tensor, sg.use_len = self.cu_use.ctypes.data, self.use_tensor.ctypes.data, self.use_len.ctypes.data
+        sg.n_uses, sg.n_tensors = self.use_tensor.size, self.n_tensors
+        return sg
+
 
 def _check_ctx_rows(ctx_k, ctx_v, plan: "AttnCtxPlan", device, k_head_stride: int, v_head_stride: int):
     """``attention_ctx`` with per-context tensors: every context's keys / values are read WHERE THEY LIE, so each tensor is held
     to what the launch assumes of all of them before anything is launched - the device, bf16, at least the context's length in
     rows, a 16-byte aligned first row, one leading dimension per operand, columns for every kv head at the shared head stride.
     Host code (tensor attributes only).  Returns (ld_ctx_k, ld_ctx_v)."""
-    n_ctx = plan.cu_ctx.size - 1
+    if plan.segmented:   # one tensor per list entry; a tensor holds at least the rows of the longest use that names it
+        import numpy as np
+        n_ctx, what_n = plan.n_tensors, "segment tensors"
+        lens = np.zeros(n_ctx, dtype=np.int64)
+        np.maximum.at(lens, plan.use_tensor, plan.use_len)
+    else:
+        n_ctx, what_n = plan.cu_ctx.size - 1, "contexts"
+        lens = plan.cu_ctx[1:] - plan.cu_ctx[:-1]
     if len(ctx_k) != n_ctx or len(ctx_v) != n_ctx:
-        raise ValueError(f"attention_ctx: {len(ctx_k)} key / {len(ctx_v)} value tensors for the plan's {n_ctx} contexts")
-    lens = plan.cu_ctx[1:] - plan.cu_ctx[:-1]
+        raise ValueError(f"attention_ctx: {len(ctx_k)} key / {len(ctx_v)} value tensors for the plan's {n_ctx} {what_n}")
     n_kv = plan.n_heads // plan.kv_group
     lds = []
     for what, ts, hs in (("keys", ctx_k, k_head_stride), ("values", ctx_v, v_head_stride)):
         ld = None
         for c, t in enumerate(ts):
-            who = f"attention_ctx: context {c} ({what})"
+            who = f"attention_ctx: {'segment tensor' if plan.segmented else 'context'} {c} ({what})"
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{who}: not a tensor")
             if t.device != device:
@@ -344,7 +372,7 @@ def _check_ctx_rows(ctx_k, ctx_v, plan: "AttnCtxPlan", device, k_head_stride: in
             if t.dim() != 2 or t.stride(1) != 1:
                 raise ValueError(f"{who}: expected 2-D rows of contiguous elements, got shape {tuple(t.shape)} strides {t.stride()}")
             if t.shape[0] < int(lens[c]):
-                raise ValueError(f"{who}: {t.shape[0]} rows, the context has {int(lens[c])}")
+                raise ValueError(f"{who}: {t.shape[0]} rows, the {'longest use of it reads' if plan.segmented else 'context has'} {int(lens[c])}")
             if t.shape[1] < (n_kv - 1) * hs + plan.head_dim:
                 raise ValueError(f"{who}: {t.shape[1]} columns do not hold {n_kv} heads of {plan.head_dim} at head stride {hs}")
             if t.data_ptr() % 16:
@@ -369,21 +397,31 @@ def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
                   q_head_stride: Optional[int] = None, k_head_stride: Optional[int] = None, v_head_stride: Optional[int] = None,
                   o_head_stride: Optional[int] = None, ctx_k_head_stride: Optional[int] = None,
                   ctx_v_head_stride: Optional[int] = None, causal: bool = True,
-                  ctx_list: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  ctx_list: Optional[torch.Tensor] = None, segments=None) -> torch.Tensor:
     """Causal attention of every sequence's own rows (q / k / v / out: 2-D views as in ``attention``) over
     [its context's rows | its own rows] (include/mjv.h, mjv_attention_ctx_bf16).  ``ctx_k`` / ``ctx_v``: every context's rows in ONE
     packed tensor each (context c at rows ``plan.cu_ctx[c]`` ...), or both a SEQUENCE of one tensor per context, read where they
     lie (ctx_k_list / ctx_v_list of the descriptor; every tensor is checked here, before any launch: ``_check_ctx_rows``).
     ``ctx_list`` (with sequences): a device int64 tensor [2, contexts] holding ``ctx_pointer_rows(ctx_k, ctx_v)`` - a caller with
     many launches over the same contexts uploads all its rows once; None: uploaded here.  ``plan``: the batch's
-    ``AttnCtxPlan``; ``workspace``: a uint8 device tensor of at least ``plan.workspace_bytes`` (the library allocates nothing)."""
+    ``AttnCtxPlan``; ``workspace``: a uint8 device tensor of at least ``plan.workspace_bytes`` (the library allocates nothing).
+    A plan built with ``segments`` makes the launch segmented (mjv_attention_ctx_seg_bf16): ``ctx_k`` / ``ctx_v`` are then the
+    sequences of SEGMENT TENSORS the plan's uses name (one per list entry, checked per use: rows >= the use's length), never
+    packed.  ``segments`` here: None = the plan's own; given, it must be what the plan was built from."""
     hd = plan.head_dim
+    if segments is not None:
+        uses = [(int(t), int(n)) for ctx in segments for t, n in ctx]
+        if not plan.segmented or uses != list(zip(plan.use_tensor.tolist(), plan.use_len.tolist())) \
+                or [len(ctx) for ctx in segments] != (plan.cu_use[1:] - plan.cu_use[:-1]).tolist():
+            raise ValueError("attention_ctx: segments differ from those the plan was built from")
     kchs = hd if ctx_k_head_stride is None else ctx_k_head_stride
     vchs = hd if ctx_v_head_stride is None else ctx_v_head_stride
     listed = [not isinstance(t, torch.Tensor) for t in (ctx_k, ctx_v)]
     if listed[0] != listed[1]:
         raise ValueError("attention_ctx: ctx_k and ctx_v must both be one packed tensor, or both a sequence of per-context tensors")
     listed = listed[0]
+    if plan.segmented and not listed:
+        raise ValueError("attention_ctx: a segmented plan needs sequences of segment tensors, not packed ctx_k / ctx_v")
     if listed:
         ctx_k, ctx_v = list(ctx_k), list(ctx_v)
         ld_ck, ld_cv = _check_ctx_rows(ctx_k, ctx_v, plan, q.device, kchs, vchs)
@@ -420,7 +458,10 @@ def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
     if workspace is not None:
         d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
     with torch.cuda.device(out.device):
-        check(load_library().mjv_attention_ctx_bf16(C.byref(d), _stream(out)), "mjv_attention_ctx_bf16")
+        if plan.segmented:
+            check(load_library().mjv_attention_ctx_seg_bf16(C.byref(d), plan.seg_desc(), _stream(out)), "mjv_attention_ctx_seg_bf16")
+        else:
+            check(load_library().mjv_attention_ctx_bf16(C.byref(d), _stream(out)), "mjv_attention_ctx_bf16")
     return out
 
 

@@ -1,7 +1,7 @@
 """Many captions per video: ``encode_video`` + ``score_captions`` against ``forward`` on the same full prompts.
 
     python tools/caption_bench.py [--m 1,2,4,8,16,64] [--reps 5] [--out FILE.json] [--matrix 8x8] [--size 448] [--frames 8]
-                                  [--context video,shared] [--no-forward]
+                                  [--context video,shared] [--no-forward] [--grow M]
 
 MJ-VIDEO-2B dims, random-init weights generated on the device (bench.py's), 8 frames @448^2, captions of 24 - 96 tokens.
 (``--m ""``: the matrix part alone.)  Per M: ms of ``encode_video``; ms of ``score_captions`` with caption_attention "shared" and "per-context" (alternated rep by rep
@@ -14,7 +14,10 @@ every pair alternated rep by rep.  ``--context video,shared`` adds the pair of c
 tokens cut down to a multiple of 64 (``encode_video``'s default) against one that holds the whole prefix the M prompts share
 (``harness.shared_prefix_len``) - per M the context tokens, caption rows, ``score_captions`` ms and encode ms of both arms, and
 the V x M matrix under ``context="video"`` / ``"shared"``, alternated rep by rep like every other pair.  ``--no-forward`` leaves
-the ``forward`` baseline out.  One JSON document on stdout (and in --out).
+the ``forward`` baseline out.  ``--grow M`` adds the growth mode (``model.extend_context``): per added frame, one
+``extend_context`` with that frame's tile against ``encode_video`` at the longer length; ``harness.score_growing_video`` over
+lengths 1 .. frames under M captions against as many ``encode_video`` + ``score_captions`` rounds; and the bytes an instruction
+branch adds against a cloned context - every pair alternated rep by rep.  One JSON document on stdout (and in --out).
 """
 import argparse
 import json
@@ -95,6 +98,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--context", default="video", help="video, or video,shared: the pair of context rules, alternated")
     ap.add_argument("--no-forward", action="store_true", help="leave the forward baseline out")
+    ap.add_argument("--grow", type=int, default=0, help="growth mode under this many captions (0: off)")
     args = ap.parse_args()
     context_arms = [a for a in args.context.split(",") if a]
     if not context_arms or any(a not in ("video", "shared") for a in context_arms):
@@ -229,6 +233,44 @@ def main():
                 encode_video_x_V=alternated({a: (lambda a=a: [model.encode_video(pv, firsts[v], context_len=klen[a][v])
                                                               for v, pv in enumerate(videos)]) for a in context_arms}, reps),
                 score_captions=alternated({a: score(ctxs[a], "in-place", "shared") for a in context_arms}, reps))
+    if args.grow:
+        from mj_video_amd.chat_input import prepare_chat_input, video_prefix
+        M, F, per = args.grow, args.frames, num_image_tokens_per_tile(cfg)
+        reps = max(2, args.reps)
+        model.caption_context_rows, model.caption_attention = "in-place", "shared"
+        end = lambda ids: int((ids[0] == synth.IMG_CONTEXT_ID).nonzero()[-1]) + 1  # noqa: E731  (the column behind the image run)
+        firsts = [synth.synth_input_ids(n * per, 900, n_caption=24) for n in range(1, F + 1)]
+        parents = [model.encode_video(px[:n], firsts[n - 1], context_len=end(firsts[n - 1])) for n in range(1, F)]
+        steps = []
+        for n in range(2, F + 1):   # n - 1 frames cached, frame n arrives
+            ids_n, K = firsts[n - 1], end(firsts[n - 1])
+            arms = alternated({"extend_context": lambda n=n: model.extend_context(parents[n - 2], ids_n, px[n - 1:n], context_len=K),
+                               "encode_video": lambda n=n: model.encode_video(px[:n], ids_n, context_len=K)}, reps)
+            steps.append(dict(frames=n, context_tokens=K, new_rows=K - parents[n - 2].P, **arms))
+            print(f"grow to {n} frames: extend_context {arms['extend_context']['median_ms']:.2f} ms, encode_video "
+                  f"{arms['encode_video']['median_ms']:.2f} ms", file=sys.stderr, flush=True)
+        del parents
+        tok = CharTokenizer()
+        captions = ["".join(chr(97 + (i * 7 + j) % 26) for j in range(24 + (i * 37) % 73)) for i in range(M)]
+        lengths = list(range(1, F + 1))
+
+        def rounds():
+            for n in lengths:
+                rows = [prepare_chat_input(cfg, tok, px[:n], video_prefix(n) + c, {}, device="cpu")[0] for c in captions]
+                ctx = model.encode_video(px[:n], rows[0], context_len=end(rows[0]))
+                ids, mask = harness.pad_right(rows, model.config.pad_token_id)
+                model.score_captions(ctx, ids.to(dev), mask.to(dev))
+
+        growing = alternated({"score_growing_video": lambda: harness.score_growing_video(model, cfg, tok, px, captions, {}, lengths=lengths),
+                              "encode_video+score_captions rounds": rounds}, reps)
+        # one video under another instruction: what a branch adds against a copy of the context
+        prompts = prompts_of(M)
+        parent = model.encode_video(px, prompts[0])
+        branch = model.extend_context(parent, prompts[0], context_len=harness.shared_prefix_len(prompts, synth.PAD_ID))
+        doc["grow"] = dict(M=M, frames=F, per_added_frame=steps, lengths=lengths, growing=growing,
+                           branch_bytes=dict(parent_tokens=parent.P, branch_tokens=branch.P, branch_adds=branch.nbytes,
+                                             branch_keeps_alive=branch.storage_nbytes, cloned_context=branch.clone().nbytes),
+                           note="host tokenisation of the prompts included in both growing arms")
     text = json.dumps(doc, indent=1)
     print(text)
     if args.out:
