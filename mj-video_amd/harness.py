@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .layout import selected_columns
 from .chat_input import prepare_chat_input, video_prefix
 
 VOTE_TYPES = ("leftvote", "rightvote", "bothbad_vote", "tievote")
@@ -153,7 +154,6 @@ def shared_prefix_len(rows, pad_id, gating_pattern=None) -> int:
     min over rows of min(r, g), r and g as ``model.score_captions`` finds them (the last token before the first ``pad_id``;
     the last occurrence of the gating pattern).  ``rows``: 1-D id sequences ([N] or [1, N] tensors / arrays), padded or not.
     Two identical prompts share everything; the cap is what keeps their selected rows among the own rows."""
-    from .modeling import find_token_for_gating
     rows = [np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r).reshape(-1) for r in rows]
     if not rows:
         raise ValueError("shared_prefix_len needs at least one prompt")
@@ -165,9 +165,7 @@ def shared_prefix_len(rows, pad_id, gating_pattern=None) -> int:
             common = min(common, int(differ[0]))
     cap = n
     for r in rows:
-        N = r.shape[0]
-        last = N - 1 if pad_id is None else (int(np.argmax(r == pad_id)) - 1) % N
-        cap = min(cap, last, find_token_for_gating(r, gating_pattern))
+        cap = min(cap, *selected_columns(r, pad_id, gating_pattern))
     k = min(common, cap)
     if k < 1:
         raise ValueError("shared_prefix_len: the prompts share no token that every row can leave to a context")

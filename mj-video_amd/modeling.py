@@ -26,10 +26,11 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import layout, ops
 from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_ROPE_QKV, EPI_SCALE_RES, EPI_SILU_MUL, HeadsDesc)
 from .chat_input import get_conv_template
 from .configuration import InternVLChatConfig, InternVLChatRewardModelingConfig, Phi3Config
+from .layout import find_token_for_gating, token_pattern  # noqa: F401  (their home is layout.py; callers import them from here)
 
 BF16 = torch.bfloat16
 
@@ -44,27 +45,6 @@ FP8_PRESETS: Dict[str, frozenset] = {
     "mxfp8-rank999": frozenset(("fc1", "fc2", "w2")),
     "mxfp8-vit": frozenset(("fc1", "fc2")),
 }
-
-# `<|im_end|><|im_start|>assistant\n` in InternLM2 token ids (moe_reward.py:45-48)
-token_pattern = [92542, 92543, 525, 11353, 364]
-
-
-def find_token_for_gating(lst, pattern=None) -> int:
-    """Index of the LAST occurrence of ``token_pattern`` in ``lst`` (moe_reward.py:50-57).  ``pattern``: another tokenizer's ids
-    of the same marker (``config.gating_token_pattern``: the Phi-3 backbone of BASELINE configs[4]); default = the reference's
-    module constant."""
-    a = np.asarray(lst)
-    pattern = token_pattern if pattern is None else list(pattern)
-    n = len(pattern)
-    if a.shape[0] >= n:
-        hit = np.ones(a.shape[0] - n + 1, dtype=bool)
-        for j, t in enumerate(pattern):
-            hit &= a[j:a.shape[0] - n + 1 + j] == t
-        idx = np.flatnonzero(hit)
-        if idx.size:
-            return int(idx[-1])
-    raise ValueError("Token pattern not found in the list.")
-
 
 @dataclass
 class CustomOutput:
@@ -155,9 +135,7 @@ class VideoContext:
         else:
             k, v, img_tail = [t.clone() for t in self.k], [t.clone() for t in self.v], self.img_tail.clone()
         if self.device.type == "cuda":
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            stream = cur.cuda_stream
+            ready, stream = _ready_now(self.device)
         return VideoContext(self.ids.copy(), self.P, k, v, img_tail, self.tail_cols.copy(), self.n_img, self.settings, ready, stream,
                             self.device)
 
@@ -178,6 +156,24 @@ class _Snapshot(NamedTuple):
     k: List[torch.Tensor]
     v: List[torch.Tensor]
     compact_values: bool = False
+
+
+def _ready_now(dev):
+    """(event, stream handle): what the current stream of ``dev`` has been given so far - rows cached now carry both, and a later
+    pass on ANOTHER stream waits for the event (``_wait_for_rows``)"""
+    cur = torch.cuda.current_stream(dev)
+    ready = torch.cuda.Event()
+    ready.record(cur)
+    return ready, cur.cuda_stream
+
+
+def _host(t: Optional[torch.Tensor]) -> Optional[np.ndarray]:
+    return None if t is None else t.detach().to("cpu").numpy()
+
+
+def _px(t: Optional[torch.Tensor]):
+    """what the token layout checks of ``pixel_values``: (shape, name of the dtype)"""
+    return None if t is None else (tuple(t.shape), str(t.dtype))
 
 
 def _up(a: np.ndarray, dev) -> torch.Tensor:
@@ -915,109 +911,34 @@ class InternVLChatRewardModeling(nn.Module):
 
         return wait
 
+    def _token_rules(self) -> layout.TokenRules:
+        pattern = getattr(self.config, "gating_token_pattern", None)
+        return layout.TokenRules(self.config.pad_token_id, self.model.img_context_token_id,
+                                 self.model.language_model.model.tok_embeddings.weight.shape[0], self.model.num_image_token,
+                                 None if pattern is None else tuple(pattern))
+
+    # the token layout lives in layout.py (pure numpy); these hand it the model's token rules and host copies of the tensors
     def _analyse_ids(self, ids: np.ndarray, am: Optional[np.ndarray], n_tiles: int, prefix_lookup=None):
-        """Validates the batch and derives everything the kernels need from the token ids (packed ids, positions, row maps).
-        ``prefix_lookup`` (``forward`` with ``prefix_cache`` on): called with the ids of the batch's common prompt prefix - the
-        longest run of leading tokens shared by every sequence that ends before any <IMG_CONTEXT> / selected row, cut to a
-        multiple of 64 - and returns True when the language tower's keys / values of exactly those tokens are cached: the
-        packed rows then leave the first ``skip`` tokens of every sequence out (positions keep counting from 0)."""
-        if ids.ndim != 2:
-            raise ValueError(f"input_ids must be [batch, seq], got {ids.shape}")
-        B, N = ids.shape
-        pad_id = self.config.pad_token_id
-        if pad_id is None and B != 1:
-            raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
-        ctx_id = self.model.img_context_token_id
-        if ctx_id is None:
-            raise ValueError("model.model.img_context_token_id is not set (eval_genai_mjvideo.py:115)")
-        if am is not None:
-            if am.shape != ids.shape:
-                raise ValueError(f"attention_mask shape {am.shape} != input_ids shape {ids.shape}")
-            am = am.astype(bool)
-        else:
-            am = np.ones((B, N), dtype=bool)
-        # ANY mask (round 6; rounds 1-5 took right-padded ones only).  The reference's eager path adds a [B, 1, N, N] mask of
-        # {causal, key is valid} (modeling_internlm2.py:96-125,907-913) and numbers positions 0 .. N - 1 WITHOUT looking at the mask
-        # (:893-898): a valid query sees exactly the valid keys at or before its column, rotated by their COLUMN indices.  Packing the
-        # valid tokens of a row in column order, with those columns as positions, is the same computation - right padding, left
-        # padding or holes alike; rows at masked columns are garbage in the reference and are never read (the selected rows must be
-        # valid: checked below).
-        lens = am.sum(axis=1)
-        if (lens <= 0).any():
-            raise ValueError("empty sequence in the batch")
-        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
-        valid = ids[am]
-        if valid.size and (int(valid.min()) < 0 or int(valid.max()) >= vocab):   # nn.Embedding raises here too
-            raise IndexError(f"token id out of range [0, {vocab}): min {int(valid.min())}, max {int(valid.max())} "
-                             "(tokenizer / checkpoint mismatch?)")
-        rs, gs, ctx, cols, loc = [], [], [], [], []
-        for b in range(B):
-            row = ids[b]
-            if pad_id is None:
-                r = N - 1
-            else:
-                r = (int(np.argmax(row == pad_id)) - 1) % N
-            g = find_token_for_gating(row, getattr(self.config, "gating_token_pattern", None))
-            if not am[b, r] or not am[b, g]:
-                raise ValueError(f"sample {b}: reward row {r} / gating row {g} lies in the masked part of the sequence "
-                                 f"({int(lens[b])} valid tokens)")
-            c = np.flatnonzero(row == ctx_id)
-            if not am[b, c].all():
-                raise ValueError(f"sample {b}: <IMG_CONTEXT> tokens in the masked part of the sequence")
-            rs.append(r)
-            gs.append(g)
-            ctx.append(c)
-            cols.append(np.flatnonzero(am[b]))                   # valid columns, in order = the packed rows of this sample
-            loc.append(np.cumsum(am[b]) - 1)                     # column -> index among the valid ones
-        n_ctx = sum(c.size for c in ctx)
-        if n_ctx != n_tiles * self.model.num_image_token:
-            raise ValueError(f"{n_ctx} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {n_tiles} tiles x "
-                             f"{self.model.num_image_token} image tokens (the reference would silently truncate, "
-                             f"modeling_internvl_chat.py:178-186)")
-        # the batch's common prompt prefix (system prompt + "Frame1: <img>": conversation.py:354-365, eval_genai_mjvideo.py:132-137)
-        skip, prefix_ids = 0, None
-        if prefix_lookup is not None:
-            lim = min(min(int(c[0]) if c.size else N for c in ctx), min(rs), min(gs))
-            masked = np.flatnonzero(~am[:, :lim].all(axis=0))     # (a prefix column must be a valid token of every sample)
-            if masked.size:
-                lim = int(masked[0])
-            if B > 1 and lim > 0:
-                differ = np.flatnonzero((ids[1:, :lim] != ids[0, :lim]).any(axis=0))
-                if differ.size:
-                    lim = int(differ[0])
-            cand = (lim // 64) * 64
-            if cand > 0:
-                prefix_ids = np.ascontiguousarray(ids[0, :cand])
-                if prefix_lookup(prefix_ids):
-                    skip = cand
-        reward_rows, gating_rows, packed, positions, img_rows = [], [], [], [], []
-        tail_rows, tail_pos, sel_in_tail_r, sel_in_tail_g = [], [], [], []
-        cu, cu_tail = [0], [0]
-        for b in range(B):
-            row, L, r, g = ids[b], int(lens[b]), rs[b], gs[b]
-            base = cu[-1] - skip           # packed row of the token at column j of this sample = base + loc[j]  (j >= skip)
-            lb = loc[b]
-            reward_rows.append(base + lb[r])
-            gating_rows.append(base + lb[g])
-            packed.append(row[cols[b][skip:]])
-            positions.append(cols[b][skip:])
-            img_rows.append(base + lb[ctx[b]])
-            cu.append(base + L)
-            # the rows from the first selected one on: all the last decoder layer needs QUERIES for (moe_reward.py:226-243)
-            t0 = int(lb[min(r, g)])          # index among the valid tokens
-            tb = cu_tail[-1] - t0
-            tail_rows.append(base + np.arange(t0, L))
-            tail_pos.append(cols[b][t0:])
-            sel_in_tail_r.append(tb + lb[r])
-            sel_in_tail_g.append(tb + lb[g])
-            cu_tail.append(tb + L)
-        return dict(B=B, N=N, total=cu[-1], max_len=int(lens.max()) - skip, skip=skip, prefix_ids=prefix_ids,
-                    ids=np.concatenate(packed).astype(np.int32), positions=np.concatenate(positions).astype(np.int32),
-                    cu=np.asarray(cu, dtype=np.int32), img_rows=np.concatenate(img_rows).astype(np.int32),
-                    sel_rows=np.asarray(reward_rows + gating_rows, dtype=np.int32),
-                    tail_rows=np.concatenate(tail_rows).astype(np.int32), tail_pos=np.concatenate(tail_pos).astype(np.int32),
-                    cu_tail=np.asarray(cu_tail, dtype=np.int32), max_tail=int(np.diff(cu_tail).max()),
-                    sel_in_tail=np.asarray(sel_in_tail_r + sel_in_tail_g, dtype=np.int32))
+        return layout.analyse_ids(self._token_rules(), ids, am, n_tiles, prefix_lookup)
+
+    def _analyse_captions(self, ids: np.ndarray, am: Optional[np.ndarray], ctxs, ci: np.ndarray, group: bool):
+        return layout.analyse_captions(self._token_rules(), ids, am, ctxs, ci, group)
+
+    def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = "", context_len: Optional[int] = None):
+        return layout.analyse_video(self._token_rules(), _px(pixel_values), _host(input_ids), _host(attention_mask), who, context_len)
+
+    def _analyse_videos(self, pixel_values, input_ids, attention_mask=None, context_len=None):
+        if isinstance(pixel_values, torch.Tensor) or isinstance(input_ids, torch.Tensor):
+            raise ValueError("encode_videos takes SEQUENCES of per-video pixel_values [tiles, 3, S, S] and prompts "
+                             "(encode_video takes one video)")
+        return layout.analyse_videos(self._token_rules(), [_px(p) for p in pixel_values], [_host(t) for t in input_ids],
+                                     None if attention_mask is None else [_host(t) for t in attention_mask], context_len)
+
+    def _analyse_extension(self, ctx: VideoContext, input_ids, pixel_values=None, attention_mask=None,
+                           context_len: Optional[int] = None):
+        if not isinstance(ctx, VideoContext):
+            raise ValueError("extend_context: the first argument is the VideoContext to extend (model.encode_video)")
+        return layout.analyse_extension(self._token_rules(), ctx, _host(input_ids), _px(pixel_values), _host(attention_mask), context_len)
 
     # -- towers ----------------------------------------------------------------------------------
     def _vision_tower(self, d, pixel_values: torch.Tensor, hidden: torch.Tensor, img_rows: torch.Tensor):
@@ -1523,10 +1444,9 @@ class InternVLChatRewardModeling(nn.Module):
             v_last = torch.zeros(P, 2 * KV * hd, dtype=BF16, device=dev)
             v_last.view(P, KV, 2, hd)[:, :, 1] = store.v[-1].view(P, KV, G + 2, hd)[:, :, G + 1]
             extra = {}
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(dev))   # a later forward on ANOTHER stream waits for the rows to exist
+        ready, stream = _ready_now(dev)
         self._prefix = dict(settings=settings, ids=prefix_ids.copy(), P=P, k=store.k, v=store.v, v_last=v_last, ready=ready,
-                            stream=torch.cuda.current_stream(dev).cuda_stream, **extra)
+                            stream=stream, **extra)
 
     # -- forward ---------------------------------------------------------------------------------
     def _cache_settings(self, padded_len: int, dev):
@@ -1557,8 +1477,6 @@ class InternVLChatRewardModeling(nn.Module):
         vit = self._vision_tower_launch(d, pixel_values)     # (needs no ids: enqueued before the host waits for them)
         input_ids, attention_mask = host_ids()
         trimmed = self.debug_probes is None
-        lc = self.config.llm_config
-        hdim = lc.hidden_size
         # what the cached prefix rows depend on besides their ids: _cache_settings, and (in front of the device) which buffer the
         # last layer's values live in
         tail_form = bool(trimmed and self.trim_last_layer and not self.norm_fusion and not self._exp8_set())
@@ -1607,7 +1525,7 @@ class InternVLChatRewardModeling(nn.Module):
         if tail_form:
             tail = _Tail(_up(info["tail_rows"], dev), _up(info["tail_pos"], dev), _up(info["cu_tail"], dev), info["max_tail"],
                          _up(info["sel_in_tail"], dev))
-        hidden = self._buf("llm_x", total, hdim, dev)
+        hidden = self._buf("llm_x", total, self.config.llm_config.hidden_size, dev)
         ops.embed_gather(ids, self.model.language_model.model.tok_embeddings.weight, hidden, self.model.img_context_token_id)
         self._vision_tower_splice(vit, hidden, img_rows)
         if self.debug_probes is not None and probes_ok:
@@ -1615,15 +1533,19 @@ class InternVLChatRewardModeling(nn.Module):
         last_x = self._language_tower(d, hidden, cu, positions, info["max_len"], sel_rows if trimmed else None, padded_len=info["N"],
                                       tail=tail, prefix=prefix)
 
-        # final RMSNorm only on the 2 rows per sample the heads read (hidden_states[-1] is post-norm, moe_reward.py:211)
+        self._norm_and_heads(d, last_x if trimmed else hidden, None if trimmed else sel_rows, outs, lo, B, dev)
+
+    def _norm_and_heads(self, d, x: torch.Tensor, sel_rows: Optional[torch.Tensor], outs, lo: int, B: int, dev):
+        """The final RMSNorm on the 2 rows per sample the heads read (hidden_states[-1] is post-norm, moe_reward.py:211), then the heads.
+        ``sel_rows`` None: ``x`` holds exactly those rows - [0, B) reward rows, [B, 2B) gating rows -; else their indices in ``x``."""
         h_r, h_g = outs["hidden_state"][lo:lo + B], outs["prompt_embedding"][lo:lo + B]
-        norm_w = self.model.language_model.model.norm.weight
-        if trimmed:   # last_x holds exactly the selected rows: [0, B) reward rows, [B, 2B) gating rows
-            ops.rmsnorm(last_x[:B], norm_w, h_r, lc.rms_norm_eps)
-            ops.rmsnorm(last_x[B:], norm_w, h_g, lc.rms_norm_eps)
+        norm_w, eps = self.model.language_model.model.norm.weight, self.config.llm_config.rms_norm_eps
+        if sel_rows is None:
+            ops.rmsnorm(x[:B], norm_w, h_r, eps)
+            ops.rmsnorm(x[B:], norm_w, h_g, eps)
         else:
-            ops.rmsnorm(hidden, norm_w, h_r, lc.rms_norm_eps, row_index=sel_rows[:B])
-            ops.rmsnorm(hidden, norm_w, h_g, lc.rms_norm_eps, row_index=sel_rows[B:])
+            ops.rmsnorm(x, norm_w, h_r, eps, row_index=sel_rows[:B])
+            ops.rmsnorm(x, norm_w, h_g, eps, row_index=sel_rows[B:])
         self._run_heads(d, h_r, h_g, outs, lo, B, dev)
 
     def _run_heads(self, d, h_r: torch.Tensor, h_g: torch.Tensor, outs, lo: int, B: int, dev):
@@ -1731,73 +1653,8 @@ class InternVLChatRewardModeling(nn.Module):
             pos = torch.arange(P, dtype=torch.int32, device=dev)
             store = _Snapshot(P, [], [], compact_values=True)
             self._language_tower(d, x, cu, pos, P, None, padded_len=N, snapshot=store)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            ready, stream = _ready_now(dev)
         return VideoContext(ids, P, store.k, store.v, img_tail, cols[n_in:].copy(), n_img, settings, ready, stream, dev)
-
-    def _analyse_extension(self, ctx: VideoContext, input_ids, pixel_values=None, attention_mask=None,
-                           context_len: Optional[int] = None):
-        """The checks of ``extend_context`` (nothing is repaired) and what its pass needs: the new context's length K, the ids
-        of the new tokens [ctx.P, K), and for every new row the row of [parent's ``img_tail`` | new tiles' projections] that
-        is spliced into it (-1: a text token).  Host code: reads shapes, dtypes and the ids."""
-        if not isinstance(ctx, VideoContext):
-            raise ValueError("extend_context: the first argument is the VideoContext to extend (model.encode_video)")
-        tiles = 0
-        if pixel_values is not None:
-            if pixel_values.dim() != 4:
-                raise ValueError(f"wrong pixel_values size: {tuple(pixel_values.shape)}")
-            if pixel_values.dtype != BF16:
-                raise TypeError(f"pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
-            tiles = int(pixel_values.shape[0])
-            if not tiles:
-                raise ValueError("pixel_values holds no tile: pass None for a pure text extension")
-        ids = input_ids.detach().to("cpu").numpy()
-        if ids.ndim == 2 and ids.shape[0] == 1:
-            ids = ids[0]
-        if ids.ndim != 1:
-            raise ValueError(f"ONE prompt ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
-        N, P0 = int(ids.shape[0]), ctx.P
-        if N <= P0:
-            raise ValueError(f"the prompt has {N} tokens, the context to extend holds {P0}: nothing to add")
-        differ = np.flatnonzero(ids[:P0] != ctx.ids)
-        if differ.size:
-            raise ValueError(f"the prompt's first {P0} token ids differ from those of the context to extend "
-                             f"(first at column {int(differ[0])})")
-        cols = np.flatnonzero(ids == self.model.img_context_token_id)
-        n_new = tiles * self.model.num_image_token
-        if cols.size != ctx.n_img + n_new:
-            raise ValueError(f"{cols.size} <IMG_CONTEXT> tokens in input_ids, but the context was built from {ctx.n_img} and "
-                             f"pixel_values holds {tiles} new tiles x {self.model.num_image_token} image tokens")
-        if context_len is None:
-            K = ((int(cols[-1]) + 1) // 64) * 64 if cols.size else 0
-        else:
-            if isinstance(context_len, bool) or not isinstance(context_len, (int, np.integer)) or not 1 <= context_len <= N - 1:
-                raise ValueError(f"context_len must be None or an int in [1, {N - 1}] (the prompt has {N} tokens), "
-                                 f"got {context_len!r}")
-            K = int(context_len)
-        if K <= P0:
-            raise ValueError(f"the extended context would hold {K} tokens, the context to extend holds {P0} already: "
-                             "context_len must be greater")
-        if attention_mask is not None:
-            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
-            if am.shape[0] != N:
-                raise ValueError(f"attention_mask of {am.shape[0]} columns, the prompt has {N}")
-            if not am[:K].all():
-                raise ValueError(f"masked column {int(np.flatnonzero(~am[:K])[0])} inside the context ({K} tokens): "
-                                 "attention_mask must be set on every context column")
-        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
-        if int(ids[P0:K].min()) < 0 or int(ids[P0:K].max()) >= vocab:
-            raise IndexError(f"token id out of range [0, {vocab})")
-        # image token j of the prompt (in column order) carries embedding j of the video: j < n_in0 lie inside the parent,
-        # n_in0 <= j < ctx.n_img are the parent's img_tail, the rest the new tiles' tokens
-        n_in0, n_in = ctx.n_img - int(ctx.tail_cols.size), int((cols < K).sum())
-        if int((cols < P0).sum()) != n_in0:
-            raise ValueError("the context to extend does not match its own image-token count")   # (cannot happen: ids agree)
-        src = np.full(K - P0, -1, dtype=np.int32)
-        src[cols[n_in0:n_in] - P0] = np.arange(n_in - n_in0)
-        return dict(ids=ids[:K].copy(), new_ids=ids[P0:K].astype(np.int32), N=N, K=K, tiles=tiles, n_new=n_new, cols=cols,
-                    n_in0=n_in0, n_in=n_in, src=src)
 
     @torch.no_grad()
     def extend_context(self, ctx: VideoContext, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor] = None,
@@ -1849,89 +1706,9 @@ class InternVLChatRewardModeling(nn.Module):
             attend = self._attend_contexts_shared([ctx], info, False, dev, segmented=True)
             store = _Snapshot(n, [], [], compact_values=True)
             self._language_tower(d, x, None, pos, 0, None, padded_len=N, snapshot=store, attend=attend)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            ready, stream = _ready_now(dev)
         return VideoContext(a["ids"], K, store.k, store.v, img_tail, cols[n_in:].copy(), int(cols.size), settings, ready, stream, dev,
                             base=ctx.segments)
-
-    def _analyse_video(self, pixel_values, input_ids, attention_mask=None, who: str = "", context_len: Optional[int] = None):
-        """The checks of ``encode_video`` / ``encode_videos`` on ONE video and its prompt ([N] or [1, N]; nothing is repaired), and
-        what the context pass needs of them: the first P ids, P (the column after the last <IMG_CONTEXT>, cut down to a multiple
-        of 64; or ``context_len``, any 1 <= K <= N - 1), the <IMG_CONTEXT> columns and how many lie inside P.  Host code: reads
-        the tensors' shapes / dtypes and the ids.  ``who``: what the messages of a many-video call start with."""
-        if pixel_values.dim() != 4:
-            raise ValueError(f"{who}wrong pixel_values size: {tuple(pixel_values.shape)}")
-        if pixel_values.dtype != BF16:
-            raise TypeError(f"{who}pixel_values must be bfloat16 like the model (got {pixel_values.dtype})")
-        ids = input_ids.detach().to("cpu").numpy()
-        if ids.ndim == 2 and ids.shape[0] == 1:
-            ids = ids[0]
-        if ids.ndim != 1:
-            raise ValueError(f"{who}ONE prompt per video ([N] or [1, N]), got input_ids of shape {tuple(input_ids.shape)}")
-        N = int(ids.shape[0])
-        cols = np.flatnonzero(ids == self.model.img_context_token_id)
-        tiles = int(pixel_values.shape[0])
-        n_img = tiles * self.model.num_image_token
-        if cols.size != n_img or n_img == 0:
-            raise ValueError(f"{who}{cols.size} <IMG_CONTEXT> tokens in input_ids but pixel_values holds {tiles} tiles x "
-                             f"{self.model.num_image_token} image tokens")
-        if context_len is None:
-            P = ((int(cols[-1]) + 1) // 64) * 64
-            if P <= 0:
-                raise ValueError(f"{who}the video tokens end at column {int(cols[-1])}: no multiple of 64 tokens to keep as a context")
-        else:
-            if isinstance(context_len, bool) or not isinstance(context_len, (int, np.integer)) or not 1 <= context_len <= N - 1:
-                raise ValueError(f"{who}context_len must be None or an int in [1, {N - 1}] (the prompt has {N} tokens), "
-                                 f"got {context_len!r}")
-            P = int(context_len)
-        if attention_mask is not None:
-            am = attention_mask.detach().to("cpu").numpy().astype(bool).reshape(-1)
-            if am.shape[0] != N:
-                raise ValueError(f"{who}attention_mask of {am.shape[0]} columns, the prompt has {N}")
-            if not am[:P].all():
-                raise ValueError(f"{who}masked column {int(np.flatnonzero(~am[:P])[0])} inside the context ({P} tokens): "
-                                 "attention_mask must be set on every context column")
-        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
-        if int(ids[:P].min()) < 0 or int(ids[:P].max()) >= vocab:
-            raise IndexError(f"{who}token id out of range [0, {vocab})")
-        return dict(ids=ids[:P].copy(), N=N, P=P, tiles=tiles, n_img=n_img, n_in=int((cols < P).sum()), cols=cols)
-
-    def _analyse_videos(self, pixel_values, input_ids, attention_mask=None, context_len=None):
-        """``encode_videos``' checks - ``_analyse_video`` video by video, every message naming its video - and the packed layout
-        of the context pass.  Host code, as ``_analyse_captions`` is."""
-        if isinstance(pixel_values, torch.Tensor) or isinstance(input_ids, torch.Tensor):
-            raise ValueError("encode_videos takes SEQUENCES of per-video pixel_values [tiles, 3, S, S] and prompts "
-                             "(encode_video takes one video)")
-        pixel_values, input_ids = list(pixel_values), list(input_ids)
-        V = len(pixel_values)
-        if not V:
-            raise ValueError("encode_videos: empty list of videos")
-        masks = [None] * V if attention_mask is None else list(attention_mask)
-        if len(input_ids) != V or len(masks) != V:
-            raise ValueError(f"encode_videos: {V} videos, {len(input_ids)} prompts" +
-                             ("" if attention_mask is None else f", {len(masks)} attention masks"))
-        if context_len is None or isinstance(context_len, (int, float, np.number)):   # one rule for every video
-            lens = [context_len] * V
-        else:
-            lens = list(context_len)
-            if len(lens) != V:
-                raise ValueError(f"encode_videos: {V} videos, context_len of {len(lens)} entries (None, one int, or one per video)")
-        vids = []
-        for v, (px, ids_t, am_t) in enumerate(zip(pixel_values, input_ids, masks)):
-            vids.append(self._analyse_video(px, ids_t, am_t, who=f"video {v}: ", context_len=lens[v]))
-            if tuple(px.shape[1:]) != tuple(pixel_values[0].shape[1:]):
-                raise ValueError(f"video {v}: tiles of {tuple(px.shape[1:])}, video 0 has {tuple(pixel_values[0].shape[1:])} "
-                                 "(one vision-tower pass takes one tile size)")
-        # the packed context rows (video v at rows cu[v] ...) and, behind them, every video's image tokens past its P
-        cu = np.concatenate([[0], np.cumsum([x["P"] for x in vids])]).astype(np.int32)
-        cu_tail = np.concatenate([[0], np.cumsum([x["n_img"] - x["n_in"] for x in vids])]).astype(np.int32)
-        total = int(cu[-1])
-        img_rows = np.concatenate([np.concatenate([cu[v] + x["cols"][:x["n_in"]], total + cu_tail[v] + np.arange(x["n_img"] - x["n_in"])])
-                                   for v, x in enumerate(vids)]).astype(np.int32)
-        return dict(videos=vids, V=V, cu=cu, cu_tail=cu_tail, total=total, max_len=max(x["P"] for x in vids),
-                    N=max(x["N"] for x in vids), ids=np.concatenate([x["ids"] for x in vids]).astype(np.int32),
-                    positions=np.concatenate([np.arange(x["P"]) for x in vids]).astype(np.int32), img_rows=img_rows)
 
     @torch.no_grad()
     def encode_videos(self, pixel_values, input_ids, attention_mask=None, context_len=None) -> List[VideoContext]:
@@ -1965,91 +1742,13 @@ class InternVLChatRewardModeling(nn.Module):
             store = _Snapshot(total, [], [], compact_values=True)
             self._language_tower(d, x, _up_pinned(info["cu"], dev), _up_pinned(info["positions"], dev), info["max_len"], None,
                                  padded_len=info["N"], snapshot=store)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            ready, stream = _ready_now(dev)
         out = []
         for v, vid in enumerate(info["videos"]):
             r0, r1, t0, t1 = int(info["cu"][v]), int(info["cu"][v + 1]), int(info["cu_tail"][v]), int(info["cu_tail"][v + 1])
             out.append(VideoContext(vid["ids"], vid["P"], [k[r0:r1] for k in store.k], [t[r0:r1] for t in store.v], tails[t0:t1],
                                     vid["cols"][vid["n_in"]:].copy(), vid["n_img"], settings, ready, stream, dev))
         return out
-
-    def _analyse_captions(self, ids: np.ndarray, am: Optional[np.ndarray], ctxs, ci: np.ndarray, group: bool):
-        """Validates every caption row against its context (nothing is repaired) and derives the packed own rows: what
-        ``_analyse_ids`` derives for whole prompts, for the columns behind each row's context.  ``group``: pack the sequences
-        context by context (the "per-context" launches address a context's sequences as one range)."""
-        M, N = ids.shape
-        pad_id = self.config.pad_token_id
-        if pad_id is None and M != 1:
-            raise ValueError("Cannot handle batch sizes > 1 if no padding token is defined.")
-        ctx_id = self.model.img_context_token_id
-        if am is not None:
-            if am.shape != ids.shape:
-                raise ValueError(f"attention_mask shape {am.shape} != input_ids shape {ids.shape}")
-            am = am.astype(bool)
-        else:
-            am = np.ones((M, N), dtype=bool)
-        vocab = self.model.language_model.model.tok_embeddings.weight.shape[0]
-        valid = ids[am]
-        if valid.size and (int(valid.min()) < 0 or int(valid.max()) >= vocab):
-            raise IndexError(f"token id out of range [0, {vocab}): min {int(valid.min())}, max {int(valid.max())}")
-        toff = np.concatenate([[0], np.cumsum([c.tail_cols.size for c in ctxs])])
-        rs, gs, own_cols, img_src = [], [], [], []
-        for b in range(M):
-            row, c = ids[b], ctxs[int(ci[b])]
-            P = c.P
-            if N < P:
-                raise ValueError(f"row {b}: {N} columns, its context {int(ci[b])} holds {P} tokens")
-            differ = np.flatnonzero(row[:P] != c.ids)
-            if differ.size:
-                raise ValueError(f"row {b}: its first {P} token ids differ from those of its context {int(ci[b])} "
-                                 f"(first at column {int(differ[0])})")
-            if not am[b, :P].all():
-                raise ValueError(f"row {b}: masked column {int(np.flatnonzero(~am[b, :P])[0])} inside its context ({P} tokens)")
-            r = N - 1 if pad_id is None else (int(np.argmax(row == pad_id)) - 1) % N
-            g = find_token_for_gating(row, getattr(self.config, "gating_token_pattern", None))
-            if r < P or g < P:
-                raise ValueError(f"row {b}: reward row {r} / gating row {g} lies inside its context ({P} tokens)")
-            if not am[b, r] or not am[b, g]:
-                raise ValueError(f"row {b}: reward row {r} / gating row {g} lies in the masked part of the sequence")
-            ic = np.flatnonzero(row == ctx_id)
-            if ic.size != c.n_img:
-                raise ValueError(f"row {b}: {ic.size} <IMG_CONTEXT> tokens, its context {int(ci[b])} was built from {c.n_img}")
-            if not am[b, ic].all():
-                raise ValueError(f"row {b}: <IMG_CONTEXT> tokens in the masked part of the sequence")
-            cols = P + np.flatnonzero(am[b, P:])
-            src = np.full(cols.shape[0], -1, dtype=np.int32)       # row of the contexts' image-tail table, or -1
-            tail = ic[ic >= P]
-            src[np.searchsorted(cols, tail)] = toff[int(ci[b])] + np.arange(tail.size)
-            rs.append(r)
-            gs.append(g)
-            own_cols.append(cols)
-            img_src.append(src)
-        order = np.argsort(ci, kind="stable") if group else np.arange(M)
-        cu, cu_tail = [0], [0]
-        reward_rows, gating_rows = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
-        sel_r, sel_g = np.zeros(M, dtype=np.int32), np.zeros(M, dtype=np.int32)
-        tail_rows, tail_pos = [], []
-        for b in order:
-            cols = own_cols[b]
-            base, L = cu[-1], cols.shape[0]
-            lr, lg = int(np.searchsorted(cols, rs[b])), int(np.searchsorted(cols, gs[b]))
-            reward_rows[b], gating_rows[b] = base + lr, base + lg
-            t0 = min(lr, lg)
-            tb = cu_tail[-1] - t0
-            tail_rows.append(base + np.arange(t0, L))
-            tail_pos.append(cols[t0:])
-            sel_r[b], sel_g[b] = tb + lr, tb + lg
-            cu.append(base + L)
-            cu_tail.append(tb + L)
-        return dict(M=M, N=N, total=cu[-1], order=order, index=ci[order].astype(np.int32),
-                    ids=np.concatenate([ids[b][own_cols[b]] for b in order]).astype(np.int32),
-                    positions=np.concatenate([own_cols[b] for b in order]).astype(np.int32),
-                    img_src=np.concatenate([img_src[b] for b in order]).astype(np.int32),
-                    cu=np.asarray(cu, dtype=np.int32), sel_rows=np.concatenate([reward_rows, gating_rows]),
-                    tail_rows=np.concatenate(tail_rows).astype(np.int32), tail_pos=np.concatenate(tail_pos).astype(np.int32),
-                    cu_tail=np.asarray(cu_tail, dtype=np.int32), sel_in_tail=np.concatenate([sel_r, sel_g]))
 
     @torch.no_grad()
     def score_captions(self, contexts, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -2105,12 +1804,11 @@ class InternVLChatRewardModeling(nn.Module):
         ids, am = self._host_ids(input_ids, attention_mask)
         info = self._analyse_captions(ids, am, ctxs, ci, group=self.caption_attention == "per-context")
         outs = self._alloc_outputs(M, dev)
-        lc = self.config.llm_config
         shared, trim = self.caption_attention == "shared", bool(self.trim_last_layer)
         with self._gemm_scratch(dev, "g0"):
             for ctx in ctxs:
                 self._wait_for_rows(dev, ctx.stream, ctx.ready, ctx.all_tensors())
-            hidden = self._buf("llm_x", info["total"], lc.hidden_size, dev)
+            hidden = self._buf("llm_x", info["total"], self.config.llm_config.hidden_size, dev)
             ops.embed_gather(_up(info["ids"], dev), self.model.language_model.model.tok_embeddings.weight, hidden,
                              self.model.img_context_token_id)
             if (info["img_src"] >= 0).any():   # the image tokens behind the contexts' boundary: their cached embeddings
@@ -2126,11 +1824,7 @@ class InternVLChatRewardModeling(nn.Module):
                              0, _up(info["sel_in_tail"], dev))
             last_x = self._language_tower(d, hidden, None, _up(info["positions"], dev), 0, _up(info["sel_rows"], dev),
                                           padded_len=info["N"], tail=tail, attend=attend)
-            h_r, h_g = outs["hidden_state"], outs["prompt_embedding"]
-            norm_w = self.model.language_model.model.norm.weight
-            ops.rmsnorm(last_x[:M], norm_w, h_r, lc.rms_norm_eps)
-            ops.rmsnorm(last_x[M:], norm_w, h_g, lc.rms_norm_eps)
-            self._run_heads(d, h_r, h_g, outs, 0, M, dev)
+            self._norm_and_heads(d, last_x, None, outs, 0, M, dev)
         self.last_packed34 = outs.pop("packed34")
         return CustomOutput(**outs)
 
