@@ -43,6 +43,8 @@
  * ABI 7, additive (MJV_ABI_VERSION stays 7; mjv_attn_ctx_desc is untouched): mjv_attn_ctx_segments with mjv_attention_ctx_seg_plan /
  * _seg_workspace_bytes / _seg_bf16 - a context of the caption pass may be the concatenation of several row ranges that live in
  * different tensors, and contexts may share ranges (a video that grows frame by frame, one video under several instructions).
+ * ABI 7, additive (MJV_ABI_VERSION stays 7): mjv_attn_readout_desc with mjv_attention_readout_plan / mjv_attention_readout_bf16 -
+ * the softmax mass of a few query rows per bin of key positions (which frames the reward rows attend to), fp32.
  */
 #ifndef MJV_H_
 #define MJV_H_
@@ -335,6 +337,60 @@ typedef struct mjv_attn_ctx_segments {
 int64_t mjv_attention_ctx_seg_plan(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, int32_t* plan_host, int64_t plan_ints);
 int64_t mjv_attention_ctx_seg_workspace_bytes(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg);
 int mjv_attention_ctx_seg_bf16(const mjv_attn_ctx_desc* d, const mjv_attn_ctx_segments* seg, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7, additive - attention READOUT: for a few query rows (the two rows per sample the reward heads read, moe_reward.py:226-243),
+ * per head, the softmax mass that falls into caller-stated bins of key positions (a frame's image tokens, the prompt text, the
+ * caption).  A compact form of `output_attentions`, which the reference declares and hard-wires to False (moe_reward.py:207): no
+ * [N, N] matrix, no values, nothing but `mass` is written.
+ *   mass[q][h][b] = sum over keys j of bin b of  exp(s_j - m) / sum_i exp(s_i - m),   s = the scores of mjv_attention_bf16 under
+ *       score_round_mode 1 / 2 (mode 0: MJV_E_ARG), m = their maximum; fp32 throughout, the probabilities are NOT rounded to bf16
+ *       (a readout, not an operand).  Bins b >= the query's bin count are written as 0 up to ld_mass.
+ *   Q : n_queries rows x n_heads heads of ALREADY ROTATED queries, row q at Q + q * ldq, head h at + h * q_head_stride.
+ *       head_dim 128 or 96 (anything else: MJV_E_UNSUPPORTED, the message names the value).
+ *   keys : the keys of query q are, in key order, rows range_row0[r] .. + range_rows[r] of tensor range_tensor[r] for
+ *       r = cu_range[q] .. cu_range[q + 1] - 1; tensor t starts at k_list[t] (DEVICE table of n_tensors device pointers, 16-byte
+ *       aligned rows), every tensor with the leading dimension ldk and the head stride k_head_stride (kv head = h / kv_group) - so
+ *       a tensor may be a column range of wider rows.  The host states EXACTLY the keys a query sees (the caller cuts the last
+ *       range at the query's own position): the kernel has no mask and never reads a row outside a stated range.
+ *   bins : query q has cu_bin[q + 1] - cu_bin[q] - 1 bins (1 to 128) with the edges bin_edge[cu_bin[q] ..]: ascending key positions
+ *       (equal neighbours = an empty bin, mass 0), the first 0, the last the query's key count.
+ *   cu_range / range_* / cu_bin / bin_edge are HOST arrays, read during the call only; everything is checked on the host before
+ *       any launch (MJV_E_ARG, the message names the query or range).  What the kernel reads is the PLAN, a device copy of the
+ *       int32 image mjv_attention_readout_plan() makes of exactly these arrays: built once per batch, handed to every layer's call -
+ *       only Q and k_list change between layers.
+ *   One workgroup per (query, kv head pair of q-heads), two passes over the keys (the maximum; then the same scores again, summed
+ *       per bin), partial sums merged in a fixed order: no atomics, no flags, equal bits run to run, and a query's bits do not
+ *       depend on the other queries of the launch.  Profiler tags attn_readout_d128 / attn_readout_d96.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mjv_attn_readout_desc {
+  const mjv_bf16* Q;
+  int64_t ldq;
+  int32_t q_head_stride;
+  int32_t n_queries, n_heads, kv_group;
+  int32_t head_dim;              /* 128 or 96 */
+  float scale;
+  int32_t score_round_mode;      /* 1 or 2 */
+  const mjv_bf16* const* k_list; /* DEVICE [n_tensors] device pointers */
+  int32_t n_tensors;
+  int32_t k_head_stride;
+  int64_t ldk;
+  const int32_t* cu_range;       /* HOST [n_queries + 1], cu_range[0] = 0 */
+  const int32_t* range_tensor;   /* HOST [n_ranges] */
+  const int32_t* range_row0;     /* HOST [n_ranges] */
+  const int32_t* range_rows;     /* HOST [n_ranges], > 0 */
+  const int32_t* cu_bin;         /* HOST [n_queries + 1] offsets into bin_edge, cu_bin[0] = 0 (a query owns bins + 1 edges) */
+  const int32_t* bin_edge;       /* HOST */
+  float* mass;                   /* DEVICE fp32 [n_queries][n_heads][ld_mass] */
+  int64_t ld_mass;               /* >= every query's bin count */
+  const int32_t* plan;           /* DEVICE copy of mjv_attention_readout_plan's output for these index arrays */
+  int64_t plan_ints;
+} mjv_attn_readout_desc;
+
+/* Reads the HOST arrays and sizes of `d` only (no device pointer; callable without a GPU).  plan_host == NULL: returns the number
+ * of int32 the plan takes; otherwise writes it (plan_ints = capacity) and returns the number written.  Negative = MJV_E_*. */
+int64_t mjv_attention_readout_plan(const mjv_attn_readout_desc* d, int32_t* plan_host, int64_t plan_ints);
+int mjv_attention_readout_bf16(const mjv_attn_readout_desc* d, void* stream);
 
 /* LayerNorm over the last dim, fp32 statistics, bf16 out (nn.LayerNorm on bf16:
  * modeling_intern_vit.py:291,293; modeling_internvl_chat.py:136).

@@ -114,6 +114,17 @@ class AttnCtxSegments(C.Structure):
                 ("n_uses", C.c_int32), ("n_tensors", C.c_int32)]
 
 
+class AttnReadoutDesc(C.Structure):
+    """mjv_attn_readout_desc (ABI 7, additive): the range / bin arrays are HOST pointers; ``Q`` / ``k_list`` / ``mass`` / ``plan``
+    device pointers"""
+    _fields_ = [("Q", C.c_void_p), ("ldq", C.c_int64), ("q_head_stride", C.c_int32), ("n_queries", C.c_int32),
+                ("n_heads", C.c_int32), ("kv_group", C.c_int32), ("head_dim", C.c_int32), ("scale", C.c_float),
+                ("score_round_mode", C.c_int32), ("k_list", C.c_void_p), ("n_tensors", C.c_int32), ("k_head_stride", C.c_int32),
+                ("ldk", C.c_int64), ("cu_range", C.c_void_p), ("range_tensor", C.c_void_p), ("range_row0", C.c_void_p),
+                ("range_rows", C.c_void_p), ("cu_bin", C.c_void_p), ("bin_edge", C.c_void_p), ("mass", C.c_void_p),
+                ("ld_mass", C.c_int64), ("plan", C.c_void_p), ("plan_ints", C.c_int64)]
+
+
 class HeadsDesc(C.Structure):
     _fields_ = [("hr", C.c_void_p), ("hg", C.c_void_p), ("ldh", C.c_int64), ("hidden", C.c_int32),
                 ("ga", C.c_void_p), ("gc", C.c_void_p), ("ldg", C.c_int64), ("gate_hidden", C.c_int32),
@@ -142,6 +153,8 @@ SYMBOLS = {
     "mjv_attention_ctx_seg_plan": (C.c_int64, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments), _VP, _I64]),
     "mjv_attention_ctx_seg_workspace_bytes": (C.c_int64, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments)]),
     "mjv_attention_ctx_seg_bf16": (C.c_int, [C.POINTER(AttnCtxDesc), C.POINTER(AttnCtxSegments), _VP]),
+    "mjv_attention_readout_plan": (C.c_int64, [C.POINTER(AttnReadoutDesc), _VP, _I64]),
+    "mjv_attention_readout_bf16": (C.c_int, [C.POINTER(AttnReadoutDesc), _VP]),
     "mjv_layernorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, _VP]),
     "mjv_rmsnorm_bf16": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP, _I32, _I32, _F, _VP]),
     "mjv_mxfp8_scale_bytes": (C.c_int64, [_I64, _I64]),

@@ -148,6 +148,27 @@ def score_pair_batch(model, config, tokenizer, examples: Sequence[dict], generat
     return model.last_packed34.view(len(examples), 2, -1)
 
 
+@torch.no_grad()
+def score_with_frame_readout(model, config, tokenizer, pixels: torch.Tensor, caption: str, generation_config: dict,
+                             tiles_per_frame=1):
+    """ONE video ([tiles, 3, S, S]) under ONE caption, scored with the frame readout on: returns ``(CustomOutput, FrameReadout)`` -
+    the scores ``model.forward`` gives with the readout off, bit for bit, and where the reward row and the gating row put their
+    attention per decoder layer and head (``FrameReadout.per_frame()``: [1, frames]).  ``tiles_per_frame``: an int, or one int
+    per frame (dynamic tiling: the tiles of one frame are summed into its column).  The model's ``frame_readout`` /
+    ``readout_tiles_per_frame`` are restored afterwards."""
+    _lib.assert_product_library()
+    dev = model.model.device
+    pv = pixels.to(torch.bfloat16)
+    ids, mask = prepare_chat_input(config, tokenizer, pv, video_prefix(pv.shape[0]) + caption, generation_config, device="cpu")
+    before = model.frame_readout, model.readout_tiles_per_frame
+    model.frame_readout, model.readout_tiles_per_frame = True, tiles_per_frame
+    try:
+        out = model.forward(pv.to(dev), ids.to(dev), mask.to(dev))
+        return out, model.last_readout
+    finally:
+        model.frame_readout, model.readout_tiles_per_frame = before
+
+
 def shared_prefix_len(rows, pad_id, gating_pattern=None) -> int:
     """The longest context the full prompts ``rows`` of ONE video can share (``model.encode_video(..., context_len=...)``): the
     length of their common prefix, capped so that every row keeps its reward row r and its gating row g outside the context -

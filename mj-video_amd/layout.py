@@ -121,6 +121,72 @@ def pack_tails(seqs):
     return np.concatenate(tail_rows).astype(np.int32), np.concatenate(tail_pos).astype(np.int32), np.asarray(cu_tail, dtype=np.int32), sel_r, sel_g
 
 
+class ReadoutRow(NamedTuple):
+    """one selected row of a sample for the frame readout, in PACKED key coordinates (key i = the sample's i-th valid column)"""
+    keys: int            # the keys the row sees: its own packed position + 1
+    edges: np.ndarray    # int32 [bins + 1]: ascending, from 0 to ``keys``; bin b = keys [edges[b], edges[b + 1])
+    fold: np.ndarray     # int32 [bins]: the public column each bin is summed into
+
+
+class ReadoutBins(NamedTuple):
+    n_frames: int        # F: public columns are frames 0 .. F - 1, then F = prompt text, F + 1 = caption
+    reward: ReadoutRow
+    gating: ReadoutRow
+
+
+READOUT_MAX_BINS = 128   # bins per query of mjv_attention_readout_bf16
+
+
+def readout_bins(rules: TokenRules, ids: np.ndarray, cols: np.ndarray, tiles_per_frame) -> ReadoutBins:
+    """The frame readout's bins of ONE sample.  ``ids``: its [N] token ids; ``cols``: its valid columns in ascending order (the
+    mask as ``analyse_ids`` packs it: right padding, left padding or holes alike); ``tiles_per_frame``: an int, or one int per
+    frame.  The sample's <IMG_CONTEXT> tokens are dealt to the frames in column order, ``tiles_per_frame[f] * tokens_per_tile``
+    each - frames may be separate runs with labels between them or one long run.  Every valid column carries a label: its frame
+    for an image token, "prompt text" for any other token up to the last image token, "caption" behind it; a bin is a maximal run
+    of packed keys with one label - text, frame 0, text, frame 1, ..., caption for a prompt with frame labels - so a bin is
+    contiguous whatever the frames look like, and ``fold`` sums the bins of one label into its public column.  Per selected row
+    (``selected_columns``) the bins are cut at the row's own position: a reward or gating row that sits before the last frame sees
+    a partial bin and none behind it.  ``ValueError`` for a ``tiles_per_frame`` that does not account for the image tokens, image
+    tokens or selected rows at masked columns, and more bins than a launch takes."""
+    ids = np.asarray(ids)
+    cols = np.asarray(cols, dtype=np.int64)
+    N, tpt = ids.shape[0], rules.tokens_per_tile
+    valid = np.zeros(N, dtype=bool)
+    valid[cols] = True
+    img = np.flatnonzero(ids == rules.ctx_id)
+    if not valid[img].all():
+        raise ValueError("frame readout: <IMG_CONTEXT> tokens in the masked part of the sequence")
+    if isinstance(tiles_per_frame, (int, np.integer)) and not isinstance(tiles_per_frame, bool):
+        per = int(tiles_per_frame) * tpt
+        if per <= 0 or img.size == 0 or img.size % per:
+            raise ValueError(f"frame readout: tiles_per_frame {int(tiles_per_frame)} x {tpt} image tokens per tile does not divide "
+                             f"the prompt's {img.size} <IMG_CONTEXT> tokens")
+        tiles = [int(tiles_per_frame)] * (img.size // per)
+    else:
+        tiles = [int(t) for t in tiles_per_frame]
+        if not tiles or min(tiles) <= 0 or sum(tiles) * tpt != img.size:
+            raise ValueError(f"frame readout: tiles_per_frame {tiles} x {tpt} image tokens per tile = {sum(tiles) * tpt}, the prompt "
+                             f"holds {img.size} <IMG_CONTEXT> tokens")
+    F = len(tiles)
+    label = np.full(N, F, dtype=np.int32)                       # prompt text
+    label[img] = np.repeat(np.arange(F, dtype=np.int32), np.asarray(tiles) * tpt)
+    label[int(img[-1]) + 1:] = F + 1                            # caption
+    lab = label[cols]                                           # per packed key
+    starts = np.concatenate([[0], np.flatnonzero(lab[1:] != lab[:-1]) + 1]).astype(np.int32)   # first key of every bin
+    loc = np.cumsum(valid) - 1
+    r, g = selected_columns(ids, rules.pad_id, rules.gating_pattern)
+    rows = []
+    for what, c in (("reward", r), ("gating", g)):
+        if not valid[c]:
+            raise ValueError(f"frame readout: {what} row {c} lies in the masked part of the sequence")
+        keys = int(loc[c]) + 1
+        nb = int(np.searchsorted(starts, keys, "left"))         # bins that start before the row's last key
+        if nb > READOUT_MAX_BINS:
+            raise ValueError(f"frame readout: the {what} row sees {nb} runs of text / frame tokens, a launch takes {READOUT_MAX_BINS} bins")
+        rows.append(ReadoutRow(keys, np.concatenate([starts[:nb], [keys]]).astype(np.int32), lab[starts[:nb]].astype(np.int32)))
+    return ReadoutBins(F, rows[0], rows[1])
+
+
 # ------------------------------------------------------------------------------------------------ the analysers
 def analyse_ids(rules: TokenRules, ids: np.ndarray, am: Optional[np.ndarray], n_tiles: int, prefix_lookup=None):
     """Validates the batch and derives everything the kernels need from the token ids (packed ids, positions, row maps).

@@ -158,6 +158,72 @@ class _Snapshot(NamedTuple):
     compact_values: bool = False
 
 
+class FrameReadout:
+    """``model.last_readout`` after a scoring call with ``model.frame_readout`` on: where the two rows the heads read
+    (moe_reward.py:226-243) put their attention, per decoder layer and head.
+    ``mass``: fp32 [B, 2, layers, heads, F_max + 2] on the device - axis 1 = (reward row, gating row); columns = the softmax mass on
+    the image tokens of frames 0 .. F_max - 1, then on the prompt text (every other token up to the last image token), then on the
+    caption (everything behind it); a row's columns sum to 1, frames a sample does not have are 0.  ``n_frames``: [B] (host).
+    Attention mass, not an explanation of the score."""
+
+    ROWS = {"reward": 0, "gating": 1}
+
+    def __init__(self, mass: torch.Tensor, n_frames: np.ndarray):
+        self.mass, self.n_frames = mass, n_frames
+
+    def per_frame(self, row: str = "reward", layers=None) -> torch.Tensor:
+        """[B, F_max]: the mass per frame of the ``row`` ("reward" / "gating") row, averaged over the heads and over ``layers``
+        (None: all of them)"""
+        if row not in self.ROWS:
+            raise ValueError(f"row {row!r} not in {tuple(self.ROWS)}")
+        m = self.mass[:, self.ROWS[row]]
+        if layers is not None:
+            m = m[:, torch.as_tensor(list(layers), dtype=torch.long, device=m.device)]
+        return m[..., :m.shape[-1] - 2].mean(dim=(1, 2))
+
+
+class _ReadoutRun:
+    """One batch's frame readout: the plan of its 2 B queries (reward rows, then gating rows), the per-layer bin masses and the
+    fold into public columns.  ``ranges``: per query its key ranges over the tensors ``key_tensors(li, k, tail)`` lists for
+    a layer (``k``: the layer's live key rows; ``tail``: the trimmed last layer)."""
+
+    def __init__(self, model, bins, ranges, key_tensors, n_tensors: int, layers: int, dev):
+        H, KV, G, hd, scale, mode = model._llm_geom()
+        rows = [b.reward for b in bins] + [b.gating for b in bins]
+        for i, (row, rr) in enumerate(zip(rows, ranges)):
+            if sum(n for _, _, n in rr) != row.keys:
+                raise RuntimeError(f"frame readout: query {i} sees {sum(n for _, _, n in rr)} key rows, its bins cover {row.keys}")
+        self.plan = ops.AttnReadoutPlan(ranges, [row.edges for row in rows], H, G, hd, mode, dev, n_tensors=n_tensors)
+        self.key_tensors, self.scale = key_tensors, scale
+        nq, nb = len(rows), self.plan.max_bins
+        self.n_frames = np.asarray([b.n_frames for b in bins], dtype=np.int64)
+        F = int(self.n_frames.max())
+        fold = np.zeros((nq, nb, F + 2), dtype=np.float32)   # bin -> public column: a sample's own text / caption labels F_b, F_b + 1
+        for i, row in enumerate(rows):                       # land in the shared columns F_max, F_max + 1
+            Fb = bins[i % len(bins)].n_frames
+            fold[i, np.arange(row.fold.size), np.where(row.fold < Fb, row.fold, row.fold - Fb + F)] = 1.0
+        self.fold = _up(fold, dev)
+        self.bin_mass = torch.empty(layers, nq, H, nb, dtype=torch.float32, device=dev)
+        self.q = model._buf("ro_q", nq, H * hd, dev)
+        self.ptr_host = torch.empty(layers, n_tensors, dtype=torch.int64, pin_memory=True)
+        self.ptr = torch.empty(layers, n_tensors, dtype=torch.int64, device=dev)
+
+    def __call__(self, li: int, q: torch.Tensor, index: torch.Tensor, k: torch.Tensor, tail: bool):
+        """layer ``li``: rows ``index`` of the rotated queries ``q`` over the layer's keys"""
+        tensors = self.key_tensors(li, k, tail)
+        self.ptr_host[li] = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64)
+        self.ptr[li].copy_(self.ptr_host[li], non_blocking=True)
+        ops.embed_gather(index, q, self.q, -1)
+        ops.attention_readout(self.q, tensors, self.plan, self.scale, self.bin_mass[li], k_list=self.ptr[li])
+
+    def result(self) -> FrameReadout:
+        L, nq, H, nb = self.bin_mass.shape
+        B = nq // 2
+        # folding contiguous bins into columns: a plain fp32 sum on the device (0 / 1 weights)
+        pub = torch.bmm(self.bin_mass.permute(1, 0, 2, 3).reshape(nq, L * H, nb), self.fold)
+        return FrameReadout(pub.view(2, B, L, H, -1).transpose(0, 1).contiguous(), self.n_frames)
+
+
 def _ready_now(dev):
     """(event, stream handle): what the current stream of ``dev`` has been given so far - rows cached now carry both, and a later
     pass on ANOTHER stream waits for the event (``_wait_for_rows``)"""
@@ -608,6 +674,14 @@ class InternVLChatRewardModeling(nn.Module):
         # per-layer base pointers per call: mjv_attn_ctx_desc.ctx_k_list / ctx_v_list); "packed" = the contexts' rows gathered
         # into one buffer per layer and operand first - its A/B partner and cross-check (equal bits), not a product mode
         self.caption_context_rows = "in-place"
+        # frame_readout: which frames the two rows the heads read attend to.  On, ``forward`` / ``score_captions`` launch
+        # mjv_attention_readout_bf16 after every decoder layer's projection - the selected rows' queries over the keys the layer
+        # has just rotated (and the cached prefix / context rows), binned per frame by layout.readout_bins - and leave a
+        # ``FrameReadout`` in ``last_readout``; every ``CustomOutput`` field keeps its bits.  Off (default): no plan, no launch,
+        # ``last_readout`` stays None.  ``readout_tiles_per_frame``: an int, or one int per frame (every sample of the batch).
+        self.frame_readout = False
+        self.readout_tiles_per_frame = 1
+        self.last_readout: Optional[FrameReadout] = None
 
     # -- construction helpers -------------------------------------------------------------------
     @classmethod
@@ -1231,17 +1305,72 @@ class InternVLChatRewardModeling(nn.Module):
 
         return attend
 
+    # The frame readout (``frame_readout``) follows the attention strategies: per query the key ranges its strategy's launch reads,
+    # cut at the query's own row, over the tensors that launch reads them from.
+    def _readout_guard(self):
+        if self.norm_fusion or self._exp8_set() or self.debug_probes is not None:
+            raise NotImplementedError("frame_readout: norm_fusion, the fp8 attention-side study and debug_probes are not built "
+                                      "into the readout")
+
+    def _readout_bins(self, ids: np.ndarray, am: Optional[np.ndarray]):
+        """layout.readout_bins of every sample (host; raises before anything is launched)"""
+        rules, N = self._token_rules(), ids.shape[1]
+        if rules.ctx_id is None:
+            raise ValueError("model.model.img_context_token_id is not set (eval_genai_mjvideo.py:115)")
+        return [layout.readout_bins(rules, ids[b], np.arange(N) if am is None else np.flatnonzero(am[b]), self.readout_tiles_per_frame)
+                for b in range(ids.shape[0])]
+
+    def _readout_live(self, bins, info, prefix, dev) -> _ReadoutRun:
+        """``_attend_live``'s keys: the cached prefix rows, then the sample's live rows up to the query's own"""
+        H, KV, G, hd, _, _ = self._llm_geom()
+        skip, B, phi3 = int(info["skip"]), info["B"], self._phi3
+        ranges = []
+        for i, row in enumerate(info["sel_rows"]):
+            base = int(info["cu"][i % B])
+            live = (1 if skip else 0, base, int(row) - base + 1)
+            ranges.append([(0, 0, skip), live] if skip else [live])
+
+        def key_tensors(li, k, tail):
+            if not skip:
+                return [k]
+            if phi3:   # column ranges of whole [q | k | v] rows / of the last layer's [k | v] rows
+                rows, c = (prefix["kv_last"], 0) if tail else (prefix["k"][li], H * hd)
+                return [rows[:, c:c + KV * hd], k]
+            return [prefix["k"][li], k]
+
+        return _ReadoutRun(self, bins, ranges, key_tensors, 2 if skip else 1, len(self.model.language_model.model.layers), dev)
+
+    def _readout_contexts(self, bins, ctxs, info, ci, dev) -> _ReadoutRun:
+        """``_attend_contexts_shared``'s keys: the context's segments where they lie (a segment several contexts hold listed
+        once), then the caption's own rows up to the query's own"""
+        entry, tensors = {}, []
+        for c in ctxs:
+            for kl, _, _ in c.segments:
+                if id(kl) not in entry:
+                    entry[id(kl)] = len(tensors)
+                    tensors.append(kl)
+        T, M = len(tensors), info["M"]
+        base = np.zeros(M, dtype=np.int64)
+        base[info["order"]] = info["cu"][:-1]      # first own row of every caption, in the original row order
+        ranges = []
+        for i, row in enumerate(info["sel_rows"]):
+            b = i % M
+            ranges.append([(entry[id(kl)], 0, n) for kl, _, n in ctxs[int(ci[b])].segments] + [(T, int(base[b]), int(row) - int(base[b]) + 1)])
+        return _ReadoutRun(self, bins, ranges, lambda li, k, tail: [kl[li] for kl in tensors] + [k], T + 1,
+                           len(self.model.language_model.model.layers), dev)
+
     def _language_tower(self, d, x: torch.Tensor, cu: torch.Tensor, positions: torch.Tensor, max_len: int,
                         sel_rows: Optional[torch.Tensor] = None, padded_len: Optional[int] = None,
                         only_layer: Optional[int] = None, tail: Optional[_Tail] = None, prefix=None,
-                        snapshot: Optional[_Snapshot] = None, attend=None):
+                        snapshot: Optional[_Snapshot] = None, attend=None, readout: Optional[_ReadoutRun] = None):
         """24 decoder layers in place on the packed rows ``x``.  With ``sel_rows`` (the 2 rows per sample the heads
         read) the LAST layer runs wo / FFN only on those rows - every other row of its output is never used
         (moe_reward.py:211,229,243) - and the [len(sel_rows), hidden] result is returned instead of ``x``.
         ``tail`` (with ``sel_rows``; ``trim_last_layer``): the last layer computes queries only for those rows.  ``attend``: the
         attention strategy (see ``_attend_live``, the default: the live keys behind ``prefix`` = the cached keys / values of the
         prompt prefix the packed rows leave out, ``prefix_cache``).  ``snapshot`` (the prefix-only pass of ``_build_prefix``, the
-        context pass of ``encode_video``): keep rows [0, P) of every layer's K / V."""
+        context pass of ``encode_video``): keep rows [0, P) of every layer's K / V.  ``readout`` (with ``sel_rows``;
+        ``frame_readout``): after every layer's projection, the attention mass of the selected rows' queries over that layer's keys."""
         dev = x.device
         lc = self.config.llm_config
         lm = self.model.language_model.model
@@ -1267,10 +1396,13 @@ class InternVLChatRewardModeling(nn.Module):
                 continue
             trim_here = li == last and sel_rows is not None and probes is None and only_layer is None
             if trim_here and tail is not None and not self.norm_fusion and not e8:
-                return (self._phi3_trimmed_last if phi3 else self._llm_trimmed_last)(d, li, layer, x, hn, rope, positions, sel_rows, tail, attend)
+                return (self._phi3_trimmed_last if phi3 else self._llm_trimmed_last)(d, li, layer, x, hn, rope, positions, sel_rows, tail, attend,
+                                                                                     readout)
             self._llm_project(d, li, layer, x, hn, qkv, q, k, rope, positions, e8)
             if snapshot is not None:
                 self._llm_snapshot(snapshot, qkv, k)
+            if readout is not None:
+                readout(li, q, sel_rows, k, False)
             attend(li, q, k, v, vhs, hn, None)
             if probes is not None and li == 0:   # operands / result of the first causal attention (parity tests)
                 probes["llm_attn0"] = dict(q=q.clone(), k=k.clone(), v=v.clone(), out=hn.clone(), kv_heads=KV)
@@ -1326,7 +1458,7 @@ class InternVLChatRewardModeling(nn.Module):
         else:
             snapshot.v.append(qkv[:P].clone())
 
-    def _llm_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend):
+    def _llm_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend, readout=None):
         """InternLM2's last layer, queries only where the heads will read (trim_last_layer): k | v projection (+ rotary on k) on
         every row, the full wqkv on the tail rows, attention of the tail's queries over all keys"""
         dev, lc = x.device, self.config.llm_config
@@ -1344,10 +1476,12 @@ class InternVLChatRewardModeling(nn.Module):
         att_t = self._buf("llm_att_tail", nt, H * hd, dev)
         ops.embed_gather(tail.rows, hn, hn_t, -1)
         ops.gemm(hn_t, layer.attention.wqkv.weight, qkv_t, EPI_ROPE_QKV, rope=(cos, sin, tail.pos, q_t, k_t, G))
+        if readout is not None:
+            readout(li, q_t, tail.sel, k, True)
         attend(li, q_t, k, kv[:, hd:], 2 * hd, att_t, tail)
         return self._llm_selected_rows(d, li, layer, x, att_t, tail.sel, sel_rows)
 
-    def _phi3_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend):
+    def _phi3_trimmed_last(self, d, li: int, layer, x, hn, rope, positions, sel_rows, tail: _Tail, attend, readout=None):
         """Phi-3's last layer under trim_last_layer: [k heads | v heads] of every row (the k heads rotated in place), q heads of
         the tail rows only"""
         dev, lc = x.device, self.config.llm_config
@@ -1364,6 +1498,8 @@ class InternVLChatRewardModeling(nn.Module):
         ops.embed_gather(tail.rows, hn, hn_t, -1)
         ops.gemm(hn_t, d["wq_last"], q_t, EPI_BIAS)
         ops.rope_heads(q_t, H, hd, cos, sin, tail.pos)
+        if readout is not None:
+            readout(li, q_t, tail.sel, kv[:, :KV * hd], True)
         attend(li, q_t, kv[:, :KV * hd], kv[:, KV * hd:], hd, att_t, tail)
         return self._llm_selected_rows(d, li, layer, x, att_t, tail.sel, sel_rows)
 
@@ -1469,7 +1605,7 @@ class InternVLChatRewardModeling(nn.Module):
             for t in tensors:
                 t.record_stream(cur)
 
-    def _forward_group(self, d, pixel_values, host_ids, outs, lo: int, probes_ok: bool):
+    def _forward_group(self, d, pixel_values, host_ids, outs, lo: int, probes_ok: bool, readout_bins=None):
         """Scores the batch on the CURRENT stream of the model's device (outputs go to rows [lo, lo+B) of ``outs``).
         ``host_ids``: function returning the (ids, mask) numpy arrays (``_host_ids_begin``) - called only after the vision
         tower's launches are out."""
@@ -1530,8 +1666,11 @@ class InternVLChatRewardModeling(nn.Module):
         self._vision_tower_splice(vit, hidden, img_rows)
         if self.debug_probes is not None and probes_ok:
             self.debug_probes["llm_embed"] = hidden.clone()
+        readout = self._readout_live(readout_bins, info, prefix, dev) if readout_bins is not None else None
         last_x = self._language_tower(d, hidden, cu, positions, info["max_len"], sel_rows if trimmed else None, padded_len=info["N"],
-                                      tail=tail, prefix=prefix)
+                                      tail=tail, prefix=prefix, readout=readout)
+        if readout is not None:
+            self.last_readout = readout.result()
 
         self._norm_and_heads(d, last_x if trimmed else hidden, None if trimmed else sel_rows, outs, lo, B, dev)
 
@@ -1782,6 +1921,9 @@ class InternVLChatRewardModeling(nn.Module):
                 if ctx.P % 64:
                     raise ValueError(f"context {c} holds {ctx.P} tokens: caption_attention 'per-context' needs a context length "
                                      "that is a multiple of 64 (prefix_len % 64 == 0); use 'shared' for a context of any length")
+        self.last_readout = None
+        if self.frame_readout:
+            self._readout_guard()
         d = self._prepare(dev)
         M, N = int(input_ids.shape[0]), int(input_ids.shape[1])
         if context_index is None:
@@ -1803,6 +1945,7 @@ class InternVLChatRewardModeling(nn.Module):
                                  "attention_scores, FFN format or device changed since encode_video): encode the video again")
         ids, am = self._host_ids(input_ids, attention_mask)
         info = self._analyse_captions(ids, am, ctxs, ci, group=self.caption_attention == "per-context")
+        bins = self._readout_bins(ids, am) if self.frame_readout else None
         outs = self._alloc_outputs(M, dev)
         shared, trim = self.caption_attention == "shared", bool(self.trim_last_layer)
         with self._gemm_scratch(dev, "g0"):
@@ -1822,8 +1965,11 @@ class InternVLChatRewardModeling(nn.Module):
             if trim:   # (the shared launch reads the tails' offsets from its plan)
                 tail = _Tail(_up(info["tail_rows"], dev), _up(info["tail_pos"], dev), None if shared else _up(info["cu_tail"], dev),
                              0, _up(info["sel_in_tail"], dev))
+            readout = self._readout_contexts(bins, ctxs, info, ci, dev) if bins is not None else None
             last_x = self._language_tower(d, hidden, None, _up(info["positions"], dev), 0, _up(info["sel_rows"], dev),
-                                          padded_len=info["N"], tail=tail, attend=attend)
+                                          padded_len=info["N"], tail=tail, attend=attend, readout=readout)
+            if readout is not None:
+                self.last_readout = readout.result()
             self._norm_and_heads(d, last_x, None, outs, 0, M, dev)
         self.last_packed34 = outs.pop("packed34")
         return CustomOutput(**outs)
@@ -1864,6 +2010,9 @@ class InternVLChatRewardModeling(nn.Module):
         dev = self.model.device
         if dev.type != "cuda":
             raise RuntimeError("InternVLChatRewardModeling.forward runs on the MI355X only: move the model with .cuda()")
+        self.last_readout = None
+        if self.frame_readout:
+            self._readout_guard()
         d = self._prepare(dev)
         if pixel_values.dtype != BF16:
             raise TypeError(f"pixel_values must be bfloat16 like the model (got {pixel_values.dtype}); "
@@ -1881,6 +2030,9 @@ class InternVLChatRewardModeling(nn.Module):
         # per-device kernel attributes), whatever the caller's current device is: model.cuda(1) works like the reference
         with self._gemm_scratch(dev, "g0"):
             host_ids = self._host_ids_begin(input_ids, attention_mask)
-            self._forward_group(d, pixel_values, host_ids, outs, 0, True)
+            bins = None
+            if self.frame_readout:   # the bins need the ids: the host waits for them before the vision tower's launches, not behind
+                bins = self._readout_bins(*host_ids())
+            self._forward_group(d, pixel_values, host_ids, outs, 0, True, readout_bins=bins)
         self.last_packed34 = outs.pop("packed34")
         return CustomOutput(**outs)

@@ -465,6 +465,110 @@ def attention_ctx(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.
     return out
 
 
+class AttnReadoutPlan:
+    """What one batch needs for ``attention_readout`` (include/mjv.h, mjv_attn_readout_desc): the HOST range / bin arrays (kept
+    alive here: the C entry reads them in every call) and the device copy of the plan ``mjv_attention_readout_plan`` makes of them.
+    Built once per batch, used by every layer's launch.  ``ranges``: per query its key ranges in key order, a range =
+    (entry of the launch's tensor list, first row, rows); ``edges``: per query its ascending bin edges (bins + 1 of them, from 0 to
+    the query's key count).  ``device`` None: the host plan only (``host``; no GPU is touched)."""
+
+    def __init__(self, ranges, edges, n_heads: int, kv_group: int, head_dim: int, score_round_mode: int, device=None,
+                 n_tensors: Optional[int] = None):
+        import numpy as np
+        ranges = [[(int(t), int(r0), int(n)) for t, r0, n in qr] for qr in ranges]
+        edges = [[int(e) for e in qe] for qe in edges]
+        if len(ranges) != len(edges):
+            raise ValueError(f"attention_readout plan: ranges for {len(ranges)} queries, bin edges for {len(edges)}")
+        flat = [r for qr in ranges for r in qr]
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))  # noqa: E731
+        self.cu_range = i32(np.concatenate([[0], np.cumsum([len(qr) for qr in ranges])]))
+        self.range_tensor, self.range_row0, self.range_rows = (i32([r[i] for r in flat]) for i in range(3))
+        self.cu_bin = i32(np.concatenate([[0], np.cumsum([len(qe) for qe in edges])]))
+        self.bin_edge = i32([e for qe in edges for e in qe])
+        self.n_queries = len(ranges)
+        self.n_tensors = int(n_tensors) if n_tensors is not None else (int(self.range_tensor.max()) + 1 if flat else 0)
+        self.n_heads, self.kv_group, self.head_dim, self.score_round_mode = n_heads, kv_group, head_dim, score_round_mode
+        self.max_bins = max((len(qe) - 1 for qe in edges), default=0)
+        lib = load_library()
+        d = self.desc()
+        n = int(lib.mjv_attention_readout_plan(C.byref(d), None, 0))
+        if n < 0:
+            check(n, "mjv_attention_readout_plan")
+        self.host = np.empty(n, dtype=np.int32)
+        check(min(0, int(lib.mjv_attention_readout_plan(C.byref(d), self.host.ctypes.data, n))), "mjv_attention_readout_plan")
+        self.plan_ints = n
+        self.device = None if device is None else torch.device(device)
+        self.plan = None if device is None else torch.from_numpy(self.host).to(self.device, non_blocking=False)
+
+    def desc(self) -> "_lib.AttnReadoutDesc":
+        d = _lib.AttnReadoutDesc()
+        d.cu_range, d.range_tensor, d.range_row0, d.range_rows = (a.ctypes.data for a in (self.cu_range, self.range_tensor, self.range_row0,
+                                                                                          self.range_rows))
+        d.cu_bin, d.bin_edge = self.cu_bin.ctypes.data, self.bin_edge.ctypes.data
+        d.n_queries, d.n_tensors = self.n_queries, self.n_tensors
+        d.n_heads, d.kv_group, d.head_dim, d.score_round_mode = self.n_heads, self.kv_group, self.head_dim, self.score_round_mode
+        return d
+
+
+def attention_readout(q: torch.Tensor, k_tensors, plan: AttnReadoutPlan, scale: float, mass: torch.Tensor,
+                      q_head_stride: Optional[int] = None, k_head_stride: Optional[int] = None,
+                      k_list: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax mass per bin of the plan's queries (include/mjv.h, mjv_attention_readout_bf16).  ``q``: 2-D view of at least
+    ``plan.n_queries`` rows of already rotated queries; ``k_tensors``: the sequence of key tensors the plan's ranges name (2-D
+    bf16 views, one leading dimension, first kv head at column 0; every range is checked against its tensor's rows here, before
+    any launch); ``mass``: fp32 [>= n_queries, n_heads, >= plan.max_bins], contiguous - rows [0, n_queries) are written, bins
+    beyond a query's count as 0.  ``k_list``: a device int64 tensor [len(k_tensors)] of the tensors' first-row addresses (a
+    caller with many launches uploads them once); None: uploaded here."""
+    import numpy as np
+    hd = plan.head_dim
+    k_tensors = list(k_tensors)
+    if plan.plan is None or plan.plan.device != q.device:
+        raise ValueError("attention_readout: the plan holds no device copy on the queries' device")
+    if len(k_tensors) != plan.n_tensors:
+        raise ValueError(f"attention_readout: {len(k_tensors)} key tensors for the plan's {plan.n_tensors}")
+    _chk_bf16(q, *k_tensors)
+    khs = hd if k_head_stride is None else k_head_stride
+    n_kv = plan.n_heads // plan.kv_group
+    need = np.zeros(plan.n_tensors, dtype=np.int64)
+    np.maximum.at(need, plan.range_tensor, plan.range_row0.astype(np.int64) + plan.range_rows)
+    ldk = None
+    for t, kt in enumerate(k_tensors):
+        who = f"attention_readout: key tensor {t}"
+        if kt.device != q.device:
+            raise ValueError(f"{who} lives on {kt.device}, the queries on {q.device}")
+        if kt.dim() != 2 or kt.stride(1) != 1:
+            raise ValueError(f"{who}: expected 2-D rows of contiguous elements, got shape {tuple(kt.shape)} strides {kt.stride()}")
+        if kt.shape[0] < int(need[t]):
+            raise ValueError(f"{who}: {kt.shape[0]} rows, a range of the plan reads up to row {int(need[t])}")
+        if kt.shape[1] < (n_kv - 1) * khs + hd:
+            raise ValueError(f"{who}: {kt.shape[1]} columns do not hold {n_kv} heads of {hd} at head stride {khs}")
+        if kt.data_ptr() % 16:
+            raise ValueError(f"{who}: its first row is not 16-byte aligned")
+        if ldk is None:
+            ldk = kt.stride(0)
+        elif kt.stride(0) != ldk and kt.shape[0] > 1:
+            raise ValueError(f"{who}: leading dimension {kt.stride(0)}, tensor 0 has {ldk} (one stride for every tensor)")
+    if q.shape[0] < plan.n_queries:
+        raise ValueError(f"attention_readout: {q.shape[0]} query rows, the plan has {plan.n_queries}")
+    if mass.dtype != torch.float32 or mass.device != q.device or mass.dim() != 3 or not mass.is_contiguous() \
+            or mass.shape[0] < plan.n_queries or mass.shape[1] != plan.n_heads or mass.shape[2] < plan.max_bins:
+        raise ValueError(f"attention_readout: mass must be a contiguous fp32 tensor [>= {plan.n_queries}, {plan.n_heads}, >= {plan.max_bins}] "
+                         f"on {q.device}")
+    if k_list is None:
+        k_list = torch.tensor([kt.data_ptr() for kt in k_tensors], dtype=torch.int64).to(q.device)
+    elif k_list.dtype != torch.int64 or k_list.device != q.device or not k_list.is_contiguous() or k_list.numel() != len(k_tensors):
+        raise ValueError(f"attention_readout: k_list must be a contiguous int64 tensor [{len(k_tensors)}] on {q.device}")
+    d = plan.desc()
+    d.Q, d.ldq, d.q_head_stride = q.data_ptr(), _row_stride(q), hd if q_head_stride is None else q_head_stride
+    d.k_list, d.ldk, d.k_head_stride = k_list.data_ptr(), ldk, khs
+    d.scale = scale
+    d.mass, d.ld_mass = mass.data_ptr(), mass.shape[2]
+    d.plan, d.plan_ints = plan.plan.data_ptr(), plan.plan_ints
+    with torch.cuda.device(q.device):
+        check(load_library().mjv_attention_readout_bf16(C.byref(d), _stream(q)), "mjv_attention_readout_bf16")
+    return mass
+
+
 def attention_set_variant(v: int) -> None:
     """This THREAD's default attention kernel: 0 automatic, 4 = register-staged round-1 kernel, 5 = round-2 choice, 6 / 7 =
     round-3 kernel with two / four waves per workgroup (all correct; tests A/B them).  1-3 are measurement variants of the
