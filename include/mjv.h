@@ -98,7 +98,8 @@ const char* mjv_arch(void);
  *   internvl2/modeling_internvl_chat.py:135-140 (mlp1)
  *   internvl2/modeling_internlm2.py:301-307 (wqkv, wo), :256-258 (w1, w3, w2)
  *   moe_reward.py:24-26 (gating hidden layers)
- * Requirements: K % 64 == 0, N % 8 == 0, lda/ldw/ldc/ldr % 8 == 0, 16-byte aligned base pointers.
+ * Requirements: K % 64 == 0, N % 8 == 0, lda/ldw/ldc/ldr % 8 == 0, 16-byte aligned base pointers (A, W, C, res; bias and
+ * scale: 8-byte aligned) - checked for every kernel family before anything is launched (MJV_E_ARG).
  * ------------------------------------------------------------------------------------------- */
 enum mjv_epilogue {
   MJV_EPI_BIAS = 0,       /* C = bf16(acc + bias)                       bias may be NULL            */
@@ -185,7 +186,9 @@ int mjv_gemm_bf16(const mjv_gemm_desc* d, void* stream);
  *     [4] split            K slices per tile through the workspace (1 = none; > 1: the slice kernel and its finish kernel)
  *     [5] grid             workgroups of the main kernel
  *     [6] persistent       1 = the persistent 256-tile kernel (grid == cus workgroups walk the tiles)
- *     [7] rope_split_after 1 = the launch writes the plain Linear and mjv_rope_split_bf16 on its rows follows */
+ *     [7] rope_split_after 1 = the launch stores the un-rotated Linear where the fused epilogue puts its result (v heads to C,
+ *                            q / k heads to rope_q / rope_k; the other columns of C untouched) and the rotary step follows in
+ *                            place on its rows of rope_q / rope_k (profiler tag rope_split) */
 int64_t mjv_gemm_plan(const mjv_gemm_desc* d, int32_t cus, int32_t* out, int64_t out_ints);
 
 /* ---------------------------------------------------------------------------------------------

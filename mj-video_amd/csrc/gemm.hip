@@ -71,6 +71,16 @@ MJV_DEV long out_row_of(const GemmArgs& p, int m) {
   return m;
 }
 
+// Rows of a ROPE_QKV problem on the kernels that have no rotary epilogue (gemm_plan.h: rope_split_after): the bf16 Linear goes where
+// the fused epilogue puts its result - a v head to its columns of C, a q / k head UN-ROTATED to its de-interleaved place in rope_q /
+// rope_k, where the in-place rotary kernel that follows finds it.  The q / k columns of C stay untouched, as on the 256-tile kernel.
+MJV_DEV u16* rope_fallback_dst(const GemmArgs& p, long m, int n) {
+  const int head = n >> 7, gs = p.rope_group + 2, grp = head / gs, within = head - grp * gs, d = n & 127;
+  if (within == p.rope_group + 1) return p.C + m * p.ldc + n;
+  if (within == p.rope_group) return p.rope_k + m * p.rope_ldk + (long)grp * 128 + d;
+  return p.rope_q + m * p.rope_ldq + ((long)grp * p.rope_group + within) * 128 + d;
+}
+
 // SiLU-mul: gate fragment (weight rows n..n+3 of a w1 block) and the matching up fragment (w3 block)
 MJV_DEV void store_silu(const GemmArgs& p, const f32x4& g, const f32x4& u, long orow, int oc, float rs = 1.f) {
   float o[4];
@@ -179,7 +189,10 @@ MJV_DEV void store_frags(const GemmArgs& p, const f32x4* acc /* [NI][NJ] */, con
         v[3] += __uint_as_float(rr[i][j][1] & 0xffff0000u);
       }
       const u32x2 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-      *(u32x2*)(p.C + orow[i] * p.ldc + ncol[j]) = o;
+      if constexpr (EPI == MJV_EPI_ROPE_QKV)
+        *(u32x2*)rope_fallback_dst(p, orow[i], ncol[j]) = o;
+      else
+        *(u32x2*)(p.C + orow[i] * p.ldc + ncol[j]) = o;
     }
   }
 }
@@ -1702,11 +1715,15 @@ int checked_plan(const mjv_gemm_desc* d, int cus, GemmPlan* plan) {
   MJV_REQUIRE(d->c_format == MJV_FMT_BF16, "gemm: an MXFP8 output needs MXFP8 operands");
   MJV_REQUIRE(d->K % 64 == 0, "gemm: K=%d must be a multiple of 64", d->K);
   MJV_REQUIRE(d->N % 8 == 0, "gemm: N=%d must be a multiple of 8", d->N);
-  MJV_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 4 == 0, "gemm: leading dims must be multiples of 8");
+  // (mjv.h: the 256-tile, persistent, tile-2 and rotary paths move 16-byte pieces of an output / residual row, the small kernels
+  // 8-byte pieces of bias / scale - one contract for every kernel family, whichever the plan picks)
+  MJV_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->ldc % 8 == 0, "gemm: leading dims must be multiples of 8");
   MJV_REQUIRE(d->lda >= d->K && d->ldw >= d->K, "gemm: lda/ldw smaller than K");
-  MJV_REQUIRE(((uintptr_t)d->A | (uintptr_t)d->W) % 16 == 0 && (uintptr_t)d->C % 8 == 0, "gemm: misaligned pointer");
+  MJV_REQUIRE(((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C) % 16 == 0, "gemm: misaligned pointer");
+  MJV_REQUIRE(((uintptr_t)d->bias | (uintptr_t)d->scale) % 8 == 0, "gemm: bias / scale must be 8-byte aligned");
   if (d->epilogue == MJV_EPI_SCALE_RES) {
-    MJV_REQUIRE(d->res != nullptr && d->ldr % 4 == 0, "gemm: SCALE_RES needs a residual");
+    MJV_REQUIRE(d->res != nullptr, "gemm: SCALE_RES needs a residual");
+    MJV_REQUIRE(d->ldr % 8 == 0 && (uintptr_t)d->res % 16 == 0, "gemm: the residual needs ldr %% 8 == 0 and a 16-byte aligned pointer");
   }
   if (d->epilogue == MJV_EPI_SILU_MUL) {
     MJV_REQUIRE(d->N % 32 == 0 && d->bias == nullptr, "gemm: SILU_MUL needs N %% 32 == 0 and no bias");
@@ -1803,7 +1820,9 @@ extern "C" int mjv_gemm_bf16(const mjv_gemm_desc* d, void* stream) {
           default: rc = launch_t2<MJV_EPI_SCALE_RES>(a, L, s); break;
         }
       } else {
-        switch (L.epilogue) {
+        // (rotary fallback: the plan's epilogue is the plain Linear, stored through rope_fallback_dst by the ROPE_QKV instantiation
+        // of the small kernels / the K-sliced finish)
+        switch (L.rope_split_after ? (int)MJV_EPI_ROPE_QKV : L.epilogue) {
           case MJV_EPI_BIAS: rc = launch<MJV_EPI_BIAS>(a, L, s); break;
           case MJV_EPI_BIAS_GELU: rc = launch<MJV_EPI_BIAS_GELU>(a, L, s); break;
           case MJV_EPI_BIAS_RELU: rc = launch<MJV_EPI_BIAS_RELU>(a, L, s); break;
@@ -1814,9 +1833,9 @@ extern "C" int mjv_gemm_bf16(const mjv_gemm_desc* d, void* stream) {
       }
     }
     if (rc == MJV_OK && L.rope_split_after)
-      rc = mjv_rope_split_bf16(d->C + r0 * d->ldc, d->ldc, d->rope_q + r0 * d->rope_ldq, d->rope_ldq, d->rope_k + r0 * d->rope_ldk,
-                               d->rope_ldk, d->rope_cos, d->rope_sin, d->rope_pos + r0, L.rows, d->N / ((d->rope_group + 2) * 128),
-                               d->rope_group, stream);
+      rc = mjv_rope_qk_inplace(d->rope_q ? d->rope_q + r0 * d->rope_ldq : nullptr, d->rope_ldq, d->rope_k + r0 * d->rope_ldk, d->rope_ldk,
+                               d->rope_cos, d->rope_sin, d->rope_pos + r0, L.rows, d->N / ((d->rope_group + 2) * 128), d->rope_group,
+                               stream);
     if (rc) return rc;
   }
   return MJV_OK;

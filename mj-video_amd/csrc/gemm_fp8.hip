@@ -559,7 +559,11 @@ int mjv_gemm_mxfp8_check(const mjv_gemm_desc* d) {
   } else {
     MJV_REQUIRE(d->ldc % 8 == 0 && (uintptr_t)d->C % 16 == 0, "gemm(mxfp8): ldc / C alignment");
   }
-  if (d->epilogue == MJV_EPI_SCALE_RES) MJV_REQUIRE(d->res != nullptr && d->ldr % 8 == 0, "gemm(mxfp8): SCALE_RES needs a residual");
+  MJV_REQUIRE(((uintptr_t)d->bias | (uintptr_t)d->scale) % 8 == 0, "gemm(mxfp8): bias / scale must be 8-byte aligned");
+  if (d->epilogue == MJV_EPI_SCALE_RES) {
+    MJV_REQUIRE(d->res != nullptr, "gemm(mxfp8): SCALE_RES needs a residual");
+    MJV_REQUIRE(d->ldr % 8 == 0 && (uintptr_t)d->res % 16 == 0, "gemm(mxfp8): the residual needs ldr %% 8 == 0 and a 16-byte aligned pointer");
+  }
   if (d->epilogue == MJV_EPI_SILU_MUL) MJV_REQUIRE(d->N % 32 == 0 && d->bias == nullptr, "gemm(mxfp8): SILU_MUL needs N %% 32 == 0 and no bias");
   return MJV_OK;
 }

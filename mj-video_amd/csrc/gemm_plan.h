@@ -34,7 +34,7 @@ struct GemmLaunch {
   int grid;              // workgroups of the main kernel
   int persistent;        // 256: gemm256p_kernel, one workgroup per CU walks the tiles
   int fuse;              // 256 unsliced: the FUSE instantiation (0 none, 1 RMSNorm, 2 LayerNorm folded in)
-  int rope_split_after;  // the launch wrote the plain Linear: mjv_rope_split_bf16 on its rows follows
+  int rope_split_after;  // the launch stored the un-rotated q / k heads in rope_q / rope_k: the in-place rotary step on its rows follows
   const char* tag;       // profiler tag, named like the kernel rocprofv3 reports
   double frac;           // this launch's share of the problem's flops and bytes
 };
@@ -155,7 +155,8 @@ inline int gemm_plan_rows(GemmPlan* p, const mjv_gemm_desc* d, int cus, const Ge
   const bool skinny = !use_big && (d->tile ? d->tile == 64 : rows <= t.skinny_max_m);
   if (!use_big && !skinny) split = gemm_slices128(d, rows, cus, t);
   // the rotary epilogue needs a whole 256-column tile staged in LDS: only the unsliced 256^2 kernel has it.  Rows that run
-  // on the other kernels (peeled tails, small problems) get the plain Linear into C and the standalone rope_split kernel.
+  // on the other kernels (peeled tails, small problems) store the un-rotated Linear where that epilogue puts its result (v to C,
+  // q / k heads to rope_q / rope_k) and the rotary step follows in place there: one contract for C whichever kernel runs a row.
   const bool rope_fallback = d->epilogue == MJV_EPI_ROPE_QKV && (!use_big || split > 1);
   const int epi = rope_fallback ? (int)MJV_EPI_BIAS : d->epilogue;
   GemmLaunch& L = gemm_plan_add(p, d, false, use_big ? 256 : skinny ? 64 : 128, epi, row0, rows, split);

@@ -94,6 +94,9 @@ struct MjvOncePerDevice {
 
 // MXFP8 operands (gemm_fp8.hip): mjv_gemm_bf16 (gemm.hip) checks, plans (gemm_plan.h) and hands descriptors that name them over
 struct GemmPlan;
+// rowops.hip: the rotary step IN PLACE on de-interleaved q / k rows that hold the un-rotated Linear (the GEMM's rotary fallback)
+int mjv_rope_qk_inplace(mjv_bf16* q, int64_t ldq, mjv_bf16* k, int64_t ldk, const mjv_bf16* cos_tab, const mjv_bf16* sin_tab,
+                        const int32_t* positions, int32_t rows, int32_t kv_heads, int32_t group, void* stream);
 int mjv_gemm_mxfp8_check(const mjv_gemm_desc* d);
 int mjv_gemm_mxfp8_run(const mjv_gemm_desc* d, const GemmPlan& plan, void* stream);
 

@@ -219,6 +219,25 @@ __global__ __launch_bounds__(256) void rope_split_kernel(const u16* __restrict__
   rotate8(src + d, dst + d, 64, cos_tab + pos * 128 + d, sin_tab + pos * 128 + d);
 }
 
+// The same step IN PLACE on the de-interleaved rows: q / k hold the UN-ROTATED heads (the GEMM's rotary fallback stores them there,
+// gemm.hip rope_fallback_dst).  A thread reads its 8 elements and their partners before it writes them; no two threads share one.
+__global__ __launch_bounds__(256) void rope_qk_inplace_kernel(u16* q, long ldq, u16* k, long ldk, const u16* __restrict__ cos_tab,
+                                                              const u16* __restrict__ sin_tab, const int* __restrict__ positions,
+                                                              int rows, int kv_heads, int group) {
+  const int slots = kv_heads * (group + 1);
+  const long total = (long)rows * slots * 8;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= total) return;
+  const int d = (int)(gid & 7) * 8;
+  const long rs = gid >> 3;
+  const int slot = (int)(rs % slots);
+  const long row = rs / slots;
+  const int kvh = slot / (group + 1), within = slot - kvh * (group + 1);
+  u16* x = (within < group) ? q + row * ldq + ((long)kvh * group + within) * 128 : k + row * ldk + (long)kvh * 128;
+  const long pos = positions[row];
+  rotate8(x + d, x + d, 64, cos_tab + pos * 128 + d, sin_tab + pos * 128 + d);
+}
+
 // Rotary embedding IN PLACE on n_heads consecutive heads of every row (the Phi-3 layout of BASELINE configs[4]'s language
 // tower: qkv_proj's columns are [q heads | k heads | v heads], so ONE launch over the first q + k heads rotates both):
 // x' = bf16(bf16(x cos) + bf16(rotate_half(x) sin)) on the first rot_dim elements of a head, bf16 tables [positions][rot_dim]
@@ -457,6 +476,20 @@ extern "C" int mjv_rope_split_bf16(const mjv_bf16* qkv, int64_t ldqkv, mjv_bf16*
   MjvProfScope ps("rope_split", s, 0, 4.0 * rows * (double)kv_heads * (group + 1) * 128);
   hipLaunchKernelGGL(rope_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, (long)ldqkv, q, (long)ldq,
                      k, (long)ldk, cos_tab, sin_tab, positions, rows, kv_heads, group);
+  return mjv_check_launch("rope_split");
+}
+
+// (internal: mjv_gemm_bf16's rotary fallback; the profiler tag stays the one of the step it replaces)
+int mjv_rope_qk_inplace(mjv_bf16* q, int64_t ldq, mjv_bf16* k, int64_t ldk, const mjv_bf16* cos_tab, const mjv_bf16* sin_tab,
+                        const int32_t* positions, int32_t rows, int32_t kv_heads, int32_t group, void* stream) {
+  MJV_REQUIRE((q || group == 0) && k && cos_tab && sin_tab && positions, "rope: null pointer");
+  MJV_REQUIRE(rows > 0 && kv_heads > 0 && group >= 0, "rope: bad sizes");
+  MJV_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0, "rope: ld alignment");
+  hipStream_t s = (hipStream_t)stream;
+  const long total = (long)rows * kv_heads * (group + 1) * 8;
+  MjvProfScope ps("rope_split", s, 0, 4.0 * rows * (double)kv_heads * (group + 1) * 128);
+  hipLaunchKernelGGL(rope_qk_inplace_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, (long)ldq, k, (long)ldk,
+                     cos_tab, sin_tab, positions, rows, kv_heads, group);
   return mjv_check_launch("rope_split");
 }
 

@@ -123,10 +123,12 @@ def test_tile_code_2_inside_and_outside_its_domain(lib):
     rows.out_rows = PTR
     grouped = desc(lib, 1000, 512, 256, BIAS, tile=2)
     grouped.out_group = 100
+    for d in outside + [rows, grouped]:
+        assert refusal(lib, d) == (-3, T2_MESSAGE)
+    # (an output that is not 16-byte aligned no longer reaches the tile-2 rule: the descriptor check refuses it for every family)
     odd_c = desc(lib, 1000, 512, 256, BIAS, tile=2)
     odd_c.C = PTR + 8
-    for d in outside + [rows, grouped, odd_c]:
-        assert refusal(lib, d) == (-3, T2_MESSAGE)
+    assert refusal(lib, odd_c) == (-1, "gemm: misaligned pointer")
 
 
 @pytest.mark.parametrize("epi", [BIAS, GELU, RELU, SILU_MUL, ROPE_QKV])
@@ -180,6 +182,35 @@ def test_the_plan_call_checks_like_the_gemm_call_and_respects_the_buffer(lib):
         assert lib.mjv_gemm_bf16(C.byref(bad), None) == -1 and lib.mjv_last_error().decode() == text
     bad = desc(lib, 512, 512, 256, ROPE_QKV, fp8=True)
     assert refusal(lib, bad) == (-1, "gemm(mxfp8): epilogue 5 unsupported")
+
+
+@pytest.mark.parametrize("family", [0, 64, 128, 256, 2, "mxfp8"])
+def test_the_header_alignment_contract_is_enforced_for_every_family(lib, family):
+    """include/mjv.h: ldc / ldr % 8, C and res 16-byte aligned, bias / scale 8-byte aligned - whichever kernel the plan would pick
+    (the 256-tile, persistent, tile-2 and rotary paths move 16-byte pieces of those rows).  Each violation is an argument error of
+    the plan query and of the GEMM call itself, before anything is launched (no GPU is needed to be refused)."""
+    fp8 = family == "mxfp8"
+    pre = "gemm(mxfp8): " if fp8 else "gemm: "
+    res_text = pre + "the residual needs ldr % 8 == 0 and a 16-byte aligned pointer"
+    c_text = pre + ("ldc / C alignment" if fp8 else "misaligned pointer")
+    violations = [(dict(ldc=1024 + 4), pre + ("ldc / C alignment" if fp8 else "leading dims must be multiples of 8")),
+                  (dict(C=PTR + 8), c_text), (dict(C=PTR + 4), c_text), (dict(ldr=1024 + 4), res_text), (dict(res=PTR + 8), res_text),
+                  (dict(bias=PTR + 4), pre + "bias / scale must be 8-byte aligned"), (dict(scale=PTR + 2), pre + "bias / scale must be 8-byte aligned")]
+    for M in (64, 1000, 65600):
+        good = desc(lib, M, 1024, 1024, SCALE_RES, fp8=fp8, tile=0 if fp8 else family)
+        good.bias = good.scale = PTR + 8
+        assert lib.mjv_gemm_plan(C.byref(good), 256, None, 0) > 0, lib.mjv_last_error()
+        for change, text in violations:
+            bad = desc(lib, M, 1024, 1024, SCALE_RES, fp8=fp8, tile=0 if fp8 else family)
+            bad.bias = bad.scale = PTR + 8
+            for k, v in change.items():
+                setattr(bad, k, v)
+            assert refusal(lib, bad) == (-1, text), (M, change)
+            assert lib.mjv_gemm_bf16(C.byref(bad), None) == -1 and lib.mjv_last_error().decode() == text, (M, change)
+    # a residual that no epilogue reads is not checked; an MX8 output keeps its own 8-byte rule
+    free = desc(lib, 1000, 1024, 1024, BIAS, fp8=fp8, tile=0 if fp8 else family)
+    free.res, free.ldr = PTR + 2, 1023
+    assert lib.mjv_gemm_plan(C.byref(free), 256, None, 0) > 0
 
 
 # ------------------------------------------------------------------------------------------- contracts over a grid

@@ -35,6 +35,12 @@ def assert_close_bf16(out, ref, max_ulps, frac_exact=0.0, atol=0.0, what=""):
 
 
 # ------------------------------------------------------------------------------------------- GEMM
+def nan_filled(*shape, device):
+    """a GEMM output before the launch: a cell that is never stored stays NaN and fails the isfinite / equal assertions (torch.empty
+    hands back whatever the caching allocator holds - in a suite that repeats a problem, often the right answer)"""
+    return torch.full(shape, float("nan"), dtype=BF, device=device)
+
+
 @pytest.fixture(params=[64, 128, 256])
 def tile(request, cuda):
     """run every GEMM test on all three tile kernels (the automatic choice would hide the 256^2 kernel at test sizes and
@@ -49,12 +55,12 @@ def tile(request, cuda):
 def test_gemm_bias(cuda, tile, M, N, K):
     from mj_video_amd import ops
     a, w, b = rnd(M, K, seed=1), rnd(N, K, std=0.05, seed=2), rnd(N, std=0.1, seed=3)
-    out = torch.empty(M, N, dtype=BF, device=cuda)
+    out = nan_filled(M, N, device=cuda)
     ops.gemm(a.to(cuda), w.to(cuda), out, ops.EPI_BIAS, bias=b.to(cuda))
     ref = (a.float() @ w.float().t() + b.float()).to(BF)
     # one rounding point, accumulation order differs: <= 1 ulp, and the vast majority bit-identical
     assert_close_bf16(out, ref, 1, frac_exact=0.98, atol=1e-6, what="gemm_bias")
-    out2 = torch.empty(M, N, dtype=BF, device=cuda)
+    out2 = nan_filled(M, N, device=cuda)
     ops.gemm(a.to(cuda), w.to(cuda), out2, ops.EPI_BIAS)
     assert_close_bf16(out2, (a.float() @ w.float().t()).to(BF), 1, frac_exact=0.98, atol=1e-6, what="gemm_nobias")
 
@@ -68,7 +74,7 @@ def test_gemm_exact_integers(cuda, tile, M, N, K):
     g = torch.Generator().manual_seed(5)
     a = torch.randint(-4, 5, (M, K), generator=g).float().to(BF)
     w = torch.randint(-3, 4, (N, K), generator=g).float().to(BF)
-    out = torch.empty(M, N, dtype=BF, device=cuda)
+    out = nan_filled(M, N, device=cuda)
     ops.gemm(a.to(cuda), w.to(cuda), out, ops.EPI_BIAS)
     ref = (a.float() @ w.float().t()).to(BF)
     assert torch.equal(out.cpu(), ref)
@@ -79,7 +85,7 @@ def test_gemm_gelu_relu(cuda, tile):
     M, N, K = 257, 512, 128
     a, w, b = rnd(M, K, seed=1), rnd(N, K, std=0.1, seed=2), rnd(N, std=0.1, seed=3)
     lin = (a.float() @ w.float().t() + b.float()).to(BF)
-    out = torch.empty(M, N, dtype=BF, device=cuda)
+    out = nan_filled(M, N, device=cuda)
     ops.gemm(a.to(cuda), w.to(cuda), out, ops.EPI_BIAS_GELU, bias=b.to(cuda))
     # two rounding points (Linear, GELU): a 1-ulp flip of the first can move the second by up to 2 ulps
     assert_close_bf16(out, F.gelu(lin.float()).to(BF), 2, frac_exact=0.97, atol=2e-3, what="gemm_gelu")
@@ -103,7 +109,7 @@ def test_gemm_gelu_is_exact_for_every_bf16_input(cuda, tile):
     for order in ("natural", "shuffled"):
         v = vals if order == "natural" else vals[torch.randperm(vals.numel(), generator=torch.Generator().manual_seed(3))]
         a = v.view(-1, 64).contiguous()
-        out = torch.empty(a.shape[0], 64, dtype=BF, device=cuda)
+        out = nan_filled(a.shape[0], 64, device=cuda)
         ops.gemm(a.to(cuda), eye.to(cuda), out, ops.EPI_BIAS_GELU)
         ref = F.gelu(a)                        # torch's CPU bf16 GELU - what the reference's nn.GELU computes on bf16 activations
         got = out.cpu()
@@ -135,7 +141,7 @@ def test_gemm_gelu_propagates_nonfinite_preactivations(cuda, tile):
     pad = (-nonfinite.numel()) % N
     cases += list(torch.cat([nonfinite, torch.ones(pad, dtype=BF)]).view(-1, N))
     for b in cases:
-        out = torch.empty(M, N, dtype=BF, device=cuda)
+        out = nan_filled(M, N, device=cuda)
         ops.gemm(a, w, out, ops.EPI_BIAS_GELU, bias=b.to(cuda))
         ref = F.gelu(b).expand(M, N)
         got = out.cpu()
@@ -181,7 +187,7 @@ def test_gemm_silu_mul(cuda, tile):
     M, FF, K = 530, 256, 128
     a, w1, w3 = rnd(M, K, seed=1), rnd(FF, K, std=0.1, seed=2), rnd(FF, K, std=0.1, seed=3)
     w13 = torch.stack([w1.view(FF // 16, 16, K), w3.view(FF // 16, 16, K)], dim=1).reshape(2 * FF, K).contiguous()
-    out = torch.empty(M, FF, dtype=BF, device=cuda)
+    out = nan_filled(M, FF, device=cuda)
     ops.gemm(a.to(cuda), w13.to(cuda), out, ops.EPI_SILU_MUL)
     g = (a.float() @ w1.float().t()).to(BF)
     u = (a.float() @ w3.float().t()).to(BF)
@@ -208,7 +214,7 @@ def test_gemm_two_per_cu_kernel_equals_the_256_tile(cuda, M, N, K):
         assert torch.equal(outs[0], outs[1]), (epi, (outs[0].float() - outs[1].float()).abs().max().item())
     x = (rnd(M, K, std=3.0, seed=7)).to(cuda)       # GELU over a wide range of pre-activations (|x| up to ~50 and tiny ones)
     x[:, ::7] *= 1e-4
-    o256, o2 = torch.empty(M, N, dtype=BF, device=cuda), torch.empty(M, N, dtype=BF, device=cuda)
+    o256, o2 = nan_filled(M, N, device=cuda), nan_filled(M, N, device=cuda)
     ops.gemm(x, w, o256, _lib.EPI_BIAS_GELU, bias=bias, tile=256)
     ops.gemm(x, w, o2, _lib.EPI_BIAS_GELU, bias=bias, tile=2)
     assert torch.equal(o256, o2)
@@ -239,9 +245,9 @@ def _persistent_case(cuda, epi, K, M, N, chunks, exact=True):
     code = ops.EPI_BIAS if epi == "bias" else ops.EPI_SILU_MUL
     cols = N if epi == "bias" else N // 2
     kw = dict(bias=b) if epi == "bias" else {}
-    one = torch.empty(M, cols, dtype=BF, device=cuda)
+    one = nan_filled(M, cols, device=cuda)
     ops.gemm(a, w, one, code, tile=256, **kw)
-    two = torch.empty(M, cols, dtype=BF, device=cuda)
+    two = nan_filled(M, cols, device=cuda)
     for lo, hi in chunks:
         ops.gemm(a[lo:hi], w, two[lo:hi], code, tile=256, **kw)
     assert torch.equal(one, two)
@@ -341,11 +347,11 @@ def test_gemm_rope_qkv_epilogue_equals_gemm_then_rope(cuda, M):
     emb = torch.cat((fr, fr), dim=-1)
     cos, sin = emb.cos().to(BF).to(cuda).contiguous(), emb.sin().to(BF).to(cuda).contiguous()
     qkv0 = torch.zeros(M, N, dtype=BF, device=cuda)
-    q0, k0 = torch.empty(M, H * D, dtype=BF, device=cuda), torch.empty(M, KV * D, dtype=BF, device=cuda)
+    q0, k0 = nan_filled(M, H * D, device=cuda), nan_filled(M, KV * D, device=cuda)
     ops.gemm(a, w, qkv0, ops.EPI_BIAS)
     ops.rope_split(qkv0, q0, k0, cos, sin, pos, KV, G)
     qkv1 = torch.zeros(M, N, dtype=BF, device=cuda)
-    q1, k1 = torch.empty(M, H * D, dtype=BF, device=cuda), torch.empty(M, KV * D, dtype=BF, device=cuda)
+    q1, k1 = nan_filled(M, H * D, device=cuda), nan_filled(M, KV * D, device=cuda)
     ops.gemm(a, w, qkv1, ops.EPI_ROPE_QKV, rope=(cos, sin, pos, q1, k1, G))
     torch.cuda.synchronize()
     assert torch.equal(q0, q1) and torch.equal(k0, k1)
@@ -649,9 +655,9 @@ def test_gemm_pipeline_race_screen(cuda):
             a = torch.randint(-3, 4, (M, K), generator=g).float().to(BF).to(cuda)
             w = torch.randint(-3, 4, (N, K), generator=g).float().to(BF).to(cuda)
             ref = (a.float() @ w.float().t()).to(BF)
-            out = torch.empty(M, N, dtype=BF, device=cuda)
+            out = nan_filled(M, N, device=cuda)
             for it in range(20):
-                out.zero_()
+                out.fill_(float("nan"))
                 ops.gemm(a, w, out, ops.EPI_BIAS)
                 assert torch.equal(out, ref), f"{M}x{N}x{K} iteration {it}: {(out != ref).sum().item()} wrong elements"
         # the persistent SiLU-mul form (8 stores per tile behind the prefetch instead of 16)
@@ -663,12 +669,12 @@ def test_gemm_pipeline_race_screen(cuda):
         w13 = torch.stack([w1.view(ff // 16, 16, K), w3.view(ff // 16, 16, K)], dim=1).reshape(2 * ff, K).contiguous().to(cuda)
         gg, uu = (a.float().cpu() @ w1.float().t()).to(BF), (a.float().cpu() @ w3.float().t()).to(BF)
         ref = (F.silu(gg) * uu)
-        first = torch.empty(M, ff, dtype=BF, device=cuda)
+        first = nan_filled(M, ff, device=cuda)
         ops.gemm(a, w13, first, ops.EPI_SILU_MUL)
         assert_close_bf16(first, ref, 3, frac_exact=0.95, atol=2e-3, what="persistent silu")
         out = torch.empty_like(first)
         for it in range(20):
-            out.zero_()
+            out.fill_(float("nan"))
             ops.gemm(a, w13, out, ops.EPI_SILU_MUL)
             assert torch.equal(out, first), f"persistent silu iteration {it}"
     finally:
@@ -796,11 +802,11 @@ def test_gemm_skinny_pipeline_race_screen(cuda):
         w = torch.randint(-2, 3, (N, K), generator=g).float().to(BF).to(cuda)
         a = a * (torch.rand(M, K, generator=g) < 0.2).to(BF).to(cuda)    # keep |sum| < 256: exact in bf16
         ref = (a.float() @ w.float().t()).to(BF)
-        out = torch.empty(M, N, dtype=BF, device=cuda)
+        out = nan_filled(M, N, device=cuda)
         for it in range(12):
             with torch.cuda.stream(side):
                 ops.gemm(big_a, big_w, big_o, ops.EPI_BIAS)
-            out.zero_()
+            out.fill_(float("nan"))
             ops.gemm(a, w, out, ops.EPI_BIAS)
             assert torch.equal(out, ref), f"M={M} N={N} K={K} iteration {it}: {(out != ref).sum().item()} wrong elements"
     torch.cuda.synchronize()
@@ -891,7 +897,7 @@ def test_gemm_plan_is_what_ran(cuda, case):
         fr = torch.einsum("i,j->ij", torch.arange(64).float(), inv)
         emb = torch.cat((fr, fr), -1)
         cos, sin = emb.cos().to(BF), emb.sin().to(BF)
-        q, k = torch.empty(M, G * D, dtype=BF, device=cuda), torch.empty(M, D, dtype=BF, device=cuda)
+        q, k = nan_filled(M, G * D, device=cuda), nan_filled(M, D, device=cuda)
         kw["rope"] = (cos.to(cuda), sin.to(cuda), pos.to(cuda), q, k, G)
     A, W = a.to(cuda), w.to(cuda)
     if fp8:

@@ -11,9 +11,11 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from mj_video_amd import ops  # noqa: E402
+from rowops_ref import padding_untouched, strided  # noqa: E402
 
 dev = torch.device("cuda", 0)
 BF = torch.bfloat16
@@ -47,6 +49,11 @@ def gemm_case():
     use_ws = rng.random() < 0.5
     integer = rng.random() < 0.4 and epi in ("bias", "nobias", "relu")
     lda = K + 8 * rng.choice([0, 0, 1, 5])
+    # output and residual rows wider than the problem (tests/test_gemm_layouts_gpu.py walks the same layouts form by form):
+    # the padding columns hold a sentinel that must survive; the residual is the output itself or a tensor of its own
+    pad_c, pad_r, apart = rng.choice([0, 8, 40]), rng.choice([0, 8, 40]), rng.random() < 0.5
+    nout = N // 2 if epi == "silu" else N
+    obuf, out = strided(torch.full((M, nout), float("nan"), dtype=BF), nout + pad_c, dev)   # (a cell never stored stays NaN)
     if integer:
         a = torch.randint(-4, 5, (M, lda), device=dev).float().to(BF)
         w = torch.randint(-3, 4, (N, K), device=dev).float().to(BF)
@@ -58,10 +65,9 @@ def gemm_case():
     av = a[:, :K]
     lin32 = av.float() @ w.float().t()
     kw = dict(tile=tile, workspace=ws if use_ws else None)
-    tag = f"gemm M={M} N={N} K={K} epi={epi} tile={tile} ws={use_ws} int={integer} lda={lda}"
+    tag = f"gemm M={M} N={N} K={K} epi={epi} tile={tile} ws={use_ws} int={integer} lda={lda} ldc=+{pad_c} ldr=+{pad_r} apart={apart}"
     try:
         if epi in ("bias", "nobias", "gelu", "relu"):
-            out = torch.empty(M, N, dtype=BF, device=dev)
             code = {"bias": ops.EPI_BIAS, "nobias": ops.EPI_BIAS, "gelu": ops.EPI_BIAS_GELU, "relu": ops.EPI_BIAS_RELU}[epi]
             ops.gemm(av, w, out, code, bias=None if epi == "nobias" else b, **kw)
             lin = (lin32 + (0 if epi == "nobias" else b.float())).to(BF)
@@ -70,14 +76,16 @@ def gemm_case():
         elif epi in ("scale_res", "res"):
             res = torch.randn(M, N, device=dev).to(BF)
             ls = (torch.randn(N, device=dev) * 0.5).to(BF)
-            out = res.clone()
+            rbuf, rin = strided(res, N + pad_r, dev) if apart else (None, out)
+            if not apart:
+                out.copy_(res)
             if epi == "scale_res":
-                ops.gemm(av, w, out, ops.EPI_SCALE_RES, bias=b, scale=ls, res=out, **kw)
+                ops.gemm(av, w, out, ops.EPI_SCALE_RES, bias=b, scale=ls, res=rin, **kw)
                 t1 = (lin32 + b.float()).to(BF).float()
                 ref = (res.float() + (t1 * ls.float()).to(BF).float()).to(BF)
                 amp = res.float().abs() + 2 * (t1 * ls.float()).abs()
             else:
-                ops.gemm(av, w, out, ops.EPI_SCALE_RES, res=out, **kw)
+                ops.gemm(av, w, out, ops.EPI_SCALE_RES, res=rin, **kw)
                 ref = (res.float() + lin32.to(BF).float()).to(BF)
                 amp = res.float().abs() + lin32.abs()
         else:
@@ -86,12 +94,13 @@ def gemm_case():
             FFD = N // 2
             w1, w3 = w[:FFD], w[FFD:]
             w13 = torch.stack([w1.view(FFD // 16, 16, K), w3.view(FFD // 16, 16, K)], dim=1).reshape(N, K).contiguous()
-            out = torch.empty(M, FFD, dtype=BF, device=dev)
             ops.gemm(av, w13, out, ops.EPI_SILU_MUL, **kw)
             g, u = (av.float() @ w1.float().t()).to(BF), (av.float() @ w3.float().t()).to(BF)
             ref = F.silu(g) * u
             amp = 2.2 * g.float().abs() * u.float().abs() + ref.float().abs()
         torch.cuda.synchronize()
+        if not padding_untouched(obuf, 0, nout) or (epi in ("scale_res", "res") and apart and not (padding_untouched(rbuf, 0, N) and torch.equal(rin, res))):
+            fails.append(tag + ": a cell outside the output was written")
         if not torch.isfinite(out.float()).all():
             fails.append(tag + ": non-finite")
         elif integer:
